@@ -3,11 +3,18 @@
 
 A "step" is ONE transformer() call (llama2.ts:205-303) = one decoded token, weights resident in HBM,
 greedy feed (-t 0, llama2.ts:476-478) from BOS at pos 0, synthetic seeded weights of the named shape.
-`value` times the device-resident loop (forward + on-device argmax, no host round trip); the same K
+`value` times the device-resident loop (forward + on-device argmax, no host round trip); the same
 steps through the blocking drop-in call l2_forward (logits handed to the host every token, as
 llama2.ts:468-478 consumes them) are reported next to it as `dropin_tok_s`.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config llama2_7b|stories110M|stories15M]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config llama2_7b|stories110M|stories15M] [--dump-outputs DIR]
+
+K is the number of timed steps whatever the context window: a run longer than seq_len decodes the sequence again from BOS, in
+passes of seq_len steps (positions 0 .. seq_len-1, the remainder last).  --dump-outputs writes what the timed decode handed back in
+its last step -- the logits of that step (float32) and the tokens its last pass chose, that step's pick the last of them
+(float64) -- as DIR/<name>.npy: the weights come from --seed, so two builds run with the same arguments can be compared output
+for output.  Both hold for N > 1 too (benchparts/worker.py): rank 0 writes the dump of the group's decode, the full logits
+after the all-gather.
 
 Everything in the JSON line is measured by this run:
   * `roofline`: the dominant kernel (rmsnorm + w1/w3 GEMV + SwiGLU) timed in situ with HIP events on the
@@ -39,7 +46,7 @@ sys.path.insert(0, ROOT)
 from llama2_ts_amd import configs, runtime  # noqa: E402
 from benchparts import profiler  # noqa: E402
 from benchparts.baselines import cpu_baseline, reference_js_figure  # noqa: E402,F401  (reference_js_figure: tests/test_bench_cpu.py)
-from benchparts.common import HBM_PEAK_GBS, avg_bytes_per_token, parity_block, under_profiler  # noqa: E402
+from benchparts.common import HBM_PEAK_GBS, avg_bytes_per_token, dump_outputs, parity_block, passes_bytes_per_token, passes_parity, step_passes, under_profiler  # noqa: E402
 from benchparts.dropin import dropin_child, dropin_direct_dispatch_off, dropin_loop, napi_dropin  # noqa: E402
 from benchparts.single import contract_keys, dispatch_note, per_kernel_block, prefill_rates, roofline_block, secondary_config, tp_prediction  # noqa: E402
 
@@ -55,11 +62,15 @@ def main():
     ap.add_argument("--no-extra", action="store_true", help="skip the secondary measurements (stories110M block, long context, sampler, prefill)")
     ap.add_argument("--no-dropin", action="store_true", help="skip the l2_forward (host round trip per token) loop")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (roofline.traffic = null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed decode's outputs (last step's logits, the tokens of its last pass) as DIR/<name>.npy")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dropin-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--worker-stage", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     # the host driver of this pool only supports dmabuf IPC: without this, RCCL and hipIpcGetMemHandle fail in ranks a launcher
     # other than ours started (set before the first HIP call of the process)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -90,8 +101,11 @@ def main():
     if args.gpus != 1:
         print("bench.py: --gpus %d: reporting the one GPU that runs" % args.gpus, file=sys.stderr)
     hdr = configs.header(args.config)
-    K = min(args.steps, hdr[6])
-    W = min(args.warmup, hdr[6])
+    S = hdr[6]
+    K = args.steps
+    W = min(args.warmup, S)
+    Kseq = min(K, S)            # the longest pass of the timed run; the legs that replay "the same steps" replay this one
+    passes = step_passes(K, S)
     device = int(os.environ.get("L2_BENCH_FORCE_DEVICE", os.environ.get("LOCAL_RANK", "0")))
 
     # counter passes first: they are child processes, and nothing in THIS process has touched the GPU yet
@@ -129,21 +143,27 @@ def main():
     if W > 1:
         ctx.bench_decode(1, 0, W - 1)
     if W > 0:
-        ctx.bench_decode(1, K - 1, 1)
-    t0 = time.perf_counter()
-    dev_ms = ctx.bench_decode(1, 0, K)         # EXACTLY K timed steps (the call returns when the last one is done)
-    wall = time.perf_counter() - t0
-    timed_tokens = ctx.bench_tokens(K)         # what the timed run decoded (checked against the reference's golden below)
+        ctx.bench_decode(1, Kseq - 1, 1)
+    # EXACTLY K timed steps (each call returns when its last step is done); between passes, untimed, what the pass decoded
+    wall, dev_ms, pass_tokens = 0.0, 0.0, []
+    for n in passes:
+        t0 = time.perf_counter()
+        dev_ms += ctx.bench_decode(1, 0, n)
+        wall += time.perf_counter() - t0
+        pass_tokens.append(ctx.bench_tokens(n))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, pass_tokens)
 
     value = K / wall
-    bpt = avg_bytes_per_token(hdr, 0, K)
+    bpt = passes_bytes_per_token(hdr, passes)
     out = {
         "metric": "decode tokens/sec + achieved HBM GB/s (% peak), 1 GPU",
         "value": round(value, 3), "unit": "tokens/s", "n_gpus": 1, "steps": K, "warmup": W,
         "ms_per_step": round(1e3 * wall / K, 5), "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "f64", "storage_dtype": "f32",
         "data": "synthetic (seeded hash generator, llama2.c-v0 layout)",
-        "config": {"workload": "%s batch-1 greedy decode, %d tokens from BOS (-t 0 -s 1 -n %d)" % (args.config, K, K),
+        "config": {"workload": "%s batch-1 greedy decode, %d tokens from BOS (-t 0 -s 1 -n %d)%s" % (
+                       args.config, K, Kseq, "" if len(passes) == 1 else ", %d passes of at most seq_len = %d steps" % (len(passes), S)),
                    "header": list(hdr), "parallelism": "single",
                    "loop": ("device-resident (forward + argmax on GPU, %s) -- `value` times THIS loop, a SURVEY.md 8(f1) extra; the contract's own call "
                             "(one blocking transformer() per token, logits to the host) is `contract_tok_s`" % dispatch_note(ctx)),
@@ -159,20 +179,19 @@ def main():
     }
 
     # the tokens of the TIMED run against the real reference's tokens for this checkpoint (fixtures are data: they travel)
-    out["parity"] = parity_block(args.config, args.seed, timed_tokens)
+    out["parity"] = passes_parity(args.config, args.seed, pass_tokens)
     if under_profiler() and os.environ.get("L2_USE_GRAPH") == "0":
         out["profiled"] = "this run was started under a profiler: eager launches instead of a recorded step per token (host-bound; read the kernel durations, not `value`)"
-    if not args.no_dropin:   # the same K steps through the blocking drop-in boundary (logits to the host every token)
-        rate, dropin_tokens = dropin_loop(ctx, K)
+    if not args.no_dropin:   # the Kseq steps of the longest pass through the blocking drop-in boundary (logits to the host every token)
+        rate, dropin_tokens = dropin_loop(ctx, Kseq)
         out["dropin_tok_s"] = round(rate, 3)
         out["parity"]["dropin_equal_to_reference_golden"] = parity_block(args.config, args.seed, dropin_tokens)["equal_to_reference_golden"]
-        out["napi_dropin_tok_s"] = napi_dropin(ctx, args.config, args.seed, K)      # the N-API addon under Node (small models: the 7B file is not written)
+        out["napi_dropin_tok_s"] = napi_dropin(ctx, args.config, args.seed, Kseq)      # the N-API addon under Node (small models: the 7B file is not written)
         if configs.checkpoint_bytes(hdr) < (2 << 30):
             out["dropin_tok_s_direct_dispatch_off"] = dropin_direct_dispatch_off(args.config, args.seed)
         contract_keys(out, bpt)
-    out["roofline"] = roofline_block(ctx, cfg, K, *traffic[args.config], trace_us.get(args.config), mfma.get(args.config))
+    out["roofline"] = roofline_block(ctx, cfg, Kseq, *traffic[args.config], trace_us.get(args.config), mfma.get(args.config))
     out["per_kernel"] = per_kernel_block(ctx, cfg)
-    S = hdr[6]
     if not args.no_extra:
         # the whole context window, position 0 .. S-1 (attention reads up to S rows per layer; split form beyond 144 rows)
         ms = ctx.bench_decode(1, 0, S)

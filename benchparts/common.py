@@ -75,6 +75,34 @@ def parity_block(name, seed, tokens):
     return out
 
 
+# ---- the timed run: --steps K whatever the context window ------------------------------------------------------
+def step_passes(K, S):
+    """The timed run of K steps as passes of at most seq_len = S steps, each from BOS at position 0 (the remainder last)."""
+    return [S] * (K // S) + ([K % S] if K % S else [])
+
+
+def passes_bytes_per_token(hdr, passes):
+    return sum(n * avg_bytes_per_token(hdr, 0, n) for n in passes) / float(sum(passes))
+
+
+def passes_parity(name, seed, pass_tokens):
+    """parity_block of the first (longest) pass; every later pass decodes the same sequence from BOS and must repeat its start."""
+    out = parity_block(name, seed, pass_tokens[0])
+    if any(list(t) != list(pass_tokens[0][:len(t)]) for t in pass_tokens[1:]):
+        out["equal_to_reference_golden"] = False
+        out["passes_differ"] = True
+    return out
+
+
+def dump_outputs(directory, ctx, pass_tokens):
+    """--dump-outputs: what the timed decode handed back in its last step -- that step's logits (float32) and the tokens of the last
+    pass, that step's pick the last of them (float64).  Read before anything else runs a step on the context."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "logits.npy"), ctx.read_state("logits").astype(np.float32))
+    np.save(os.path.join(directory, "tokens.npy"), np.asarray(pass_tokens[-1]).astype(np.float64))
+
+
 def host_cpu_model():
     try:
         for line in open("/proc/cpuinfo"):

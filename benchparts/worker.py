@@ -15,7 +15,7 @@ import sys
 import threading
 import time
 
-from .common import HBM_PEAK_GBS, ROOT, avg_bytes_per_token, parity_block, under_profiler
+from .common import HBM_PEAK_GBS, ROOT, dump_outputs, passes_bytes_per_token, passes_parity, step_passes, under_profiler
 from .ranks import MARK, deadlines
 from .single import committed_prediction, dispatch_note
 
@@ -69,7 +69,9 @@ def worker(args):
     if under_profiler():
         os.environ.setdefault("L2_USE_GRAPH", "0")
     hdr = configs.header(args.config)
-    K, W = min(args.steps, hdr[6]), min(args.warmup, hdr[6])
+    K, W = args.steps, min(args.warmup, hdr[6])
+    Kseq = min(K, hdr[6])       # the longest pass of the timed run (bench.py: passes of at most seq_len steps from BOS)
+    passes = step_passes(K, hdr[6])
     shards = stage != "replicas"
     device = int(os.environ.get("L2_BENCH_FORCE_DEVICE", local_rank))   # test hook: several ranks on one GPU
     cfg = runtime.Config(hdr)
@@ -128,7 +130,7 @@ def worker(args):
     toks, err = [], ""
     try:
         ctx.synth_fill(args.seed)
-        toks = ctx.decode_greedy(1, 0, min(16, K)).tolist()
+        toks = ctx.decode_greedy(1, 0, min(16, Kseq)).tolist()
     except Exception as e:      # noqa: BLE001
         err = "%s: %s" % (type(e).__name__, e)
     every = [None] * world
@@ -163,26 +165,33 @@ def worker(args):
     if W > 1:
         ctx.bench_decode(1, 0, W - 1)
     if W > 0:
-        ctx.bench_decode(1, K - 1, 1)
-    sync_all()
-    t0 = time.perf_counter()
-    dev_ms = ctx.bench_decode(1, 0, K)         # EXACTLY K timed steps
-    sync_all()
-    wall = time.perf_counter() - t0
-    timed_tokens = ctx.bench_tokens(K)
+        ctx.bench_decode(1, Kseq - 1, 1)
+    # EXACTLY K timed steps, every rank in step at both ends of each pass; between passes, untimed, what the pass decoded
+    wall, dev_ms, pass_tokens = 0.0, 0.0, []
+    for n in passes:
+        sync_all()
+        t0 = time.perf_counter()
+        dev_ms += ctx.bench_decode(1, 0, n)
+        sync_all()
+        wall += time.perf_counter() - t0
+        pass_tokens.append(ctx.bench_tokens(n))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, pass_tokens)
     t = torch.tensor([wall, dev_ms], dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall, dev_ms = float(t[0]), float(t[1])
 
     tokens_total = K if shards else K * world
     value = tokens_total / wall
-    bpt = avg_bytes_per_token(hdr, 0, K)
+    bpt = passes_bytes_per_token(hdr, passes)
     per_gpu_streams = 1 if shards else world
     out = {
         "metric": "decode tokens/sec (whole job)", "value": round(value, 3), "unit": "tokens/s", "n_gpus": world, "steps": K, "warmup": W,
         "ms_per_step": round(1e3 * wall / K, 5), "higher_is_better": True, "scaling": "strong" if shards else "weak", "vs_baseline": None,
         "dtype": "f64", "storage_dtype": "f32", "data": "synthetic (seeded hash generator, llama2.c-v0 layout)",
-        "config": {"workload": "%s batch-1 greedy decode, %d tokens from BOS (-t 0 -s 1 -n %d)" % (args.config, K, K), "header": list(hdr),
+        "config": {"workload": "%s batch-1 greedy decode, %d tokens from BOS (-t 0 -s 1 -n %d)%s" % (
+                       args.config, K, Kseq, "" if len(passes) == 1 else ", %d passes of at most seq_len = %d steps" % (len(passes), hdr[6])),
+                   "header": list(hdr),
                    "parallelism": ("tp%d" % world) if shards else "replicas%d" % world,
                    "loop": ("device-resident (forward + argmax on GPU); tensor-parallel step: %s; dispatch: %s" % (ctx.tp_mode(), dispatch_note(ctx))
                             if shards else "device-resident (forward + argmax on GPU, %s)" % dispatch_note(ctx)),
@@ -192,7 +201,7 @@ def worker(args):
         "hbm_gbs_end_to_end": round(bpt * value / 1e9 / per_gpu_streams, 2),
         "hbm_frac_end_to_end": round(bpt * value / 1e9 / per_gpu_streams / HBM_PEAK_GBS / (world if shards else 1), 4),
     }
-    out["parity"] = parity_block(args.config, args.seed, timed_tokens)
+    out["parity"] = passes_parity(args.config, args.seed, pass_tokens)
     ranks = [None] * world
     dist.all_gather_object(ranks, {"rank": rank, "device": device, "tp_mode": ctx.tp_mode_id()})
     out["tp"] = {"ranks": world, "sharded": bool(shards), "stage": stage, "l2_tp_mode": sorted({r["tp_mode"] for r in ranks}),
@@ -203,7 +212,7 @@ def worker(args):
         out["profiled"] = "this run was started under a profiler: eager launches (host-bound; read the kernel durations, not `value`)"
     # ---- roofline of the dominant kernel on THIS rank's shard, in situ (every rank decodes: the step's exchanges are collective)
     try:
-        kus, nlaunch = ctx.bench_dominant_in_situ(1, 0, min(K, 64))
+        kus, nlaunch = ctx.bench_dominant_in_situ(1, 0, min(Kseq, 64))
         kb = shard_dominant_bytes(cfg, world if shards else 1)
         ach = kb / (kus * 1e-6) / 1e9
         out["roofline"] = {"bound": "hbm", "achieved": round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,

@@ -16,6 +16,8 @@ What it does:
      RunState buffers and KV cache for the tiny shapes.
 
 Nothing derived from the reference's source text is written into the repo -- only numbers.
+`--strip-host` writes the one fixture that is text: the project's own host/l2_backend.ts after the reference's type
+stripper (tests/golden/l2_backend_stripped.json, strip_host below).
 """
 import hashlib
 import json
@@ -266,7 +268,28 @@ def time_reference(names):
             json.dump(out, f, indent=1)
 
 
+HOST_TS = os.path.join("llama2.ts_amd", "host", "l2_backend.ts")
+
+
+def strip_host():
+    """tests/golden/l2_backend_stripped.json: llama2.ts_amd/host/l2_backend.ts with its types stripped by the reference's own
+    stripper (strip_types), next to the sha256 of the source it was made from -- tests/test_host_cpu.py checks the stripped module
+    against l2_backend.mjs without the reference.  Rerun after every edit of l2_backend.ts."""
+    src = os.path.join(ROOT, HOST_TS)
+    out = os.path.join(WORK, "l2_backend.stripped.mjs")
+    strip_types(src, out)
+    with open(src, "rb") as f:
+        src_sha = hashlib.sha256(f.read()).hexdigest()
+    with open(out) as f:
+        code = f.read()
+    with open(os.path.join(GOLD, "l2_backend_stripped.json"), "w") as f:
+        json.dump({"source": HOST_TS, "source_sha256": src_sha, "code": code,
+                   "stripper": "sucrase 3.21.0 bundled in the reference's t348.mjs ({transforms: [typescript], disableESTransforms: true})"}, f, indent=1)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--strip-host":
+        return strip_host()
     if len(sys.argv) > 1 and sys.argv[1] == "--speed":
         subprocess.run(["make", "-C", os.path.join(ROOT, "oracle")], check=True, stdout=subprocess.DEVNULL)
         return time_reference(sys.argv[2:] or ["stories15M", "stories110M", "llama2_7b_L2"])

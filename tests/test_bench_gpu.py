@@ -87,6 +87,47 @@ def test_bench_two_ranks_replicas_on_one_gpu():
     assert j["roofline"]["bound"] == "hbm" and j["roofline"]["frac"] > 0 and "cpu_baseline" in j
 
 
+def _check_dump(d, config, n_tokens):
+    """--dump-outputs: the last step's logits (float32, vocab_size of them) and the last pass's tokens (float64), which are the
+    reference's greedy tokens from BOS; the last of them is the pick of the dumped logits."""
+    import numpy as np
+    lg, tk = np.load(os.path.join(d, "logits.npy")), np.load(os.path.join(d, "tokens.npy"))
+    g = json.load(open(os.path.join(ROOT, "tests", "golden", config + ".json")))
+    assert lg.dtype == np.float32 and lg.shape == (abs(g["header"][5]),) and np.isfinite(lg).all()
+    assert tk.dtype == np.float64 and tk.shape == (n_tokens,)
+    assert tk.tolist() == g["argmax"][:n_tokens]
+    assert int(np.argmax(lg)) == int(tk[-1])
+
+
+def test_bench_steps_past_seq_len_and_dump(tmp_path):
+    """--steps sets the number of timed steps even above seq_len (stories15M: 256): 300 steps are a pass of 256 and one of 44, each
+    from BOS, both checked against the reference's tokens; --dump-outputs writes what the last step handed back."""
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "stories15M", "--steps", "300", "--warmup", "2", "--no-extra",
+                        "--no-pmc", "--no-dropin", "--no-cpu-baseline", "--dump-outputs", str(d)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    j = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][0])
+    assert j["steps"] == 300 and j["ms_per_step"] > 0 and abs(j["value"] - 1e3 / j["ms_per_step"]) / j["value"] < 0.01
+    assert "2 passes" in j["config"]["workload"]
+    assert j["parity"]["steps_checked"] == 256 and j["parity"]["equal_to_reference_golden"] is True and "passes_differ" not in j["parity"]
+    _check_dump(str(d), "stories15M", 44)
+
+
+def test_bench_two_ranks_steps_past_seq_len_and_dump(tmp_path):
+    """The same through the multi-rank workers (benchparts/worker.py): two replica ranks of stories15M, 300 timed steps, rank 0 dumps."""
+    d = tmp_path / "dump"
+    env = dict(os.environ, L2_BENCH_FORCE_DEVICE="0")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", "29631", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "300", "--warmup", "2",
+           "--config", "stories15M", "--no-cpu-baseline", "--dump-outputs", str(d)]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, env=env)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    j = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][0])
+    assert j["n_gpus"] == 2 and j["config"]["parallelism"] == "replicas2" and j["steps"] == 300 and j["ms_per_step"] > 0
+    assert j["parity"]["steps_checked"] == 256 and j["parity"]["equal_to_reference_golden"] is True
+    _check_dump(str(d), "stories15M", 44)
+
+
 CO_RESIDENCY = ("never raised its flag", "did not arrive", "failed its self-test", "exchange timed out")
 
 
@@ -105,11 +146,11 @@ def _retry_once(fn):
         return fn(1)
 
 
-def _two_ranks(extra_env, tmp_path, port):
+def _two_ranks(extra_env, tmp_path, port, extra_argv=()):
     env = dict(os.environ, L2_BENCH_FORCE_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "16", "--warmup", "2",
-           "--config", "llama2_7b_L2", "--no-cpu-baseline"]
+           "--config", "llama2_7b_L2", "--no-cpu-baseline", *extra_argv]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, env=env)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
@@ -126,6 +167,17 @@ def test_bench_tensor_parallel_flow_with_two_processes_on_one_gpu(tmp_path):
         j = _two_ranks({"L2_TP_IPC_DIR": str(meet), "L2_TP_WAIT_S": "10"}, tmp_path, 29613 + 20 * k)
         assert j["n_gpus"] == 2 and j["scaling"] == "strong" and j["config"]["parallelism"] == "tp2" and j["value"] > 0, j.get("note")
         assert "peer-to-peer" in j["config"]["loop"] and "note" not in j, j.get("note")
+    _retry_once(attempt)
+
+
+def test_bench_tensor_parallel_dump(tmp_path):
+    """--dump-outputs of a tensor-parallel run: rank 0 writes the gathered logits of the group's last step and its tokens."""
+    def attempt(k):
+        meet, d = tmp_path / ("meet%d" % k), tmp_path / ("dump%d" % k)
+        meet.mkdir()
+        j = _two_ranks({"L2_TP_IPC_DIR": str(meet), "L2_TP_WAIT_S": "10"}, tmp_path, 29651 + 20 * k, ("--dump-outputs", str(d)))
+        assert j["config"]["parallelism"] == "tp2" and j["steps"] == 16 and j["parity"]["equal_to_reference_golden"] is True, j.get("note")
+        _check_dump(str(d), "llama2_7b_L2", 16)
     _retry_once(attempt)
 
 

@@ -78,18 +78,20 @@ def test_typescript_declarations_cover_the_addon(built):
 
 def test_typescript_twin_erases_to_the_module(built, tmp_path):
     """`host stays TypeScript` taken literally: l2_backend.ts is the same module in erasable-syntax TypeScript.  Stripping its types
-    with the stripper the reference itself ships (sucrase inside /root/reference/t348.mjs -- what the reference's own loader does to
+    with the stripper the reference itself ships (sucrase inside the reference's t348.mjs -- what the reference's own loader does to
     llama2.ts at import) must give l2_backend.mjs back token for token (comments and whitespace aside), and the stripped file must
-    load under this box's Node with the same exports."""
+    load under this box's Node with the same exports.  The stripped file is tests/golden/l2_backend_stripped.json, written by
+    oracle/make_goldens.py --strip-host from the l2_backend.ts whose sha256 it records."""
+    import hashlib
+    import json
     import re
-    import sys
-    if not os.path.exists("/root/reference/t348.mjs"):
-        pytest.skip("the reference (and its bundled type stripper) is not on this box")
-    sys.path.insert(0, os.path.join(ROOT, "oracle"))
-    import make_goldens as mg
     host = os.path.join(ROOT, "llama2.ts_amd", "host")
+    g = json.load(open(os.path.join(ROOT, "tests", "golden", "l2_backend_stripped.json")))
+    assert g["source"] == os.path.join("llama2.ts_amd", "host", "l2_backend.ts")
+    assert hashlib.sha256(open(os.path.join(host, "l2_backend.ts"), "rb").read()).hexdigest() == g["source_sha256"], \
+        "l2_backend.ts changed since its stripped fixture was made: rerun oracle/make_goldens.py --strip-host"
     out = tmp_path / "l2_backend.stripped.mjs"
-    mg.strip_types(os.path.join(host, "l2_backend.ts"), str(out))
+    out.write_text(g["code"])
 
     def code(src):
         src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)

@@ -1,9 +1,11 @@
-"""INTEGRATION.md section 1, EXECUTED: the four-edit patch applied to the real /root/reference/llama2.ts (in /tmp), types
-stripped with the reference's own sucrase, run under Node with a recording stub in place of the N-API addon
-(tools/run_integration_patch.py).  Build-container only: the GPU box has neither /root/reference nor this need -- there
-tests/test_cli_gpu.py drives the real addon.  Reference lines: llama2.ts:433 (readConfig), :435 (readWeights), :468 (the call)."""
+"""INTEGRATION.md section 1, EXECUTED: the four-edit patch applied to the real reference llama2.ts, types stripped with the
+reference's own sucrase, run under Node with a recording stub in place of the N-API addon (tools/run_integration_patch.py).
+The reference's source is not part of this repository: tools/run_integration_patch.py --record stored what the stub recorded
+in tests/golden/integration_patch.json, with the sha256 of the patch and stub that ran; the checks below hold that recording
+against the checkpoint the repository's generator writes.  On a GPU box tests/test_cli_gpu.py drives the real addon.
+Reference lines: llama2.ts:433 (readConfig), :435 (readWeights), :468 (the call)."""
+import json
 import os
-import shutil
 import struct
 import sys
 
@@ -13,8 +15,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-pytestmark = pytest.mark.skipif(not os.path.exists("/root/reference/llama2.ts") or shutil.which("node") is None,
-                                reason="needs the reference checkout and node (build container only)")
+import oracle_lib as O  # noqa: E402
 
 
 def fnv(b):
@@ -25,10 +26,15 @@ def fnv(b):
 
 
 @pytest.mark.parametrize("hdr", [(64, 176, 2, 4, 4, -512, 64), (64, 176, 3, 4, 4, 512, 64)])
-def test_patched_reference_drives_the_addon_interface(hdr):
+def test_patched_reference_drives_the_addon_interface(hdr, tmp_path):
     import run_integration_patch as rip
+    g = json.load(open(os.path.join(ROOT, "tests", "golden", "integration_patch.json")))
+    assert g["patch_sha256"] == rip.patch_sha256(), "the patch or the stub changed since the recording: rerun tools/run_integration_patch.py --record"
+    run = next(r for r in g["runs"] if tuple(r["header"]) == hdr)
     steps = 16
-    rec = rip.run(hdr, 1, steps)
+    assert run["steps"] == steps and run["seed"] == 1
+    rec = dict(run["record"], checkpoint=str(tmp_path / "model.bin"))
+    O.synth_write(hdr, run["seed"], rec["checkpoint"])
     d, h, L, H, _, V, S = hdr
     shared, V = V > 0, abs(V)
     # the library is opened once, the context created from the 7 header ints verbatim (sign of vocab_size kept)

@@ -10,9 +10,12 @@ What it does, all of it in a scratch directory under /tmp (nothing derived from 
   4. runs the patched reference on a synthetic checkpoint with a RECORDING STUB in place of l2_napi.node: a CommonJS module
      with the addon's entry points (`open / create / upload / forward`) that writes down what it is called with and fills
      state.logits with a deterministic one-hot so that the reference's own loop picks known tokens.
-It prints the recording as JSON; tests/test_integration_patch_cpu.py asserts on it (14 kinds in file order, layer indices, float
-counts, contents == the file's bytes at the right offsets whatever the view's byteOffset, one forward per position).
+It prints the recording as JSON.  `--record` writes the recordings of the shapes tests/test_integration_patch_cpu.py checks to
+tests/golden/integration_patch.json, with the sha256 of the patch and stub that made them (patch_sha256); the test asserts on them
+(14 kinds in file order, layer indices, float counts, contents == the file's bytes at the right offsets whatever the view's
+byteOffset, one forward per position).  Rerun it after every edit of PATCH or STUB.
 """
+import hashlib
 import json
 import os
 import shutil
@@ -63,6 +66,26 @@ process.on('exit', () => fs.writeFileSync(process.env.L2_RECORD, JSON.stringify(
 """
 
 
+# the shapes of the recorded runs (shared and unshared classifier), their seed and length
+RECORDED = [(64, 176, 2, 4, 4, -512, 64), (64, 176, 3, 4, 4, 512, 64)]
+SEED, STEPS = 1, 16
+GOLDEN = os.path.join(ROOT, "tests", "golden", "integration_patch.json")
+
+
+def patch_sha256():
+    return hashlib.sha256(json.dumps([PATCH, STUB]).encode("utf8")).hexdigest()
+
+
+def record():
+    runs = []
+    for hdr in RECORDED:
+        rec = run(hdr, SEED, STEPS)
+        del rec["checkpoint"]
+        runs.append({"header": list(hdr), "seed": SEED, "steps": STEPS, "record": rec})
+    with open(GOLDEN, "w") as f:
+        json.dump({"patch_sha256": patch_sha256(), "runs": runs}, f, indent=1)
+
+
 def apply_patch(src_text):
     out = src_text
     for anchor, how, text in PATCH:
@@ -104,5 +127,7 @@ def run(hdr, seed, steps):
 
 
 if __name__ == "__main__":
+    if sys.argv[1:] == ["--record"]:
+        sys.exit(record())
     hdr = tuple(int(v) for v in sys.argv[1:8]) if len(sys.argv) >= 8 else (64, 176, 2, 4, 4, -512, 64)
     print(json.dumps(run(hdr, 1, 16))[:4000])
