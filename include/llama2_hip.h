@@ -24,7 +24,9 @@ extern "C" {
 /* 3 (round 5): l2_bench_tokens, option keys 5-7, L2_TP_SOLO_ID / l2_tp_mode 5 and the L2_TP_FENCED switch joined the surface after 2 -- a
  * binding built against it refuses an older library at open() (l2_abi_version), not at the first call that is missing.
  * 4 (round 5): option key L2_OPT_AQL_QUEUE
- * 5 (round 6): option keys L2_OPT_PREFILL_F32_MFMA, L2_OPT_CHECK_POS; l2_dispatch_reason */
+ * 5 (round 6): option keys L2_OPT_PREFILL_F32_MFMA, L2_OPT_CHECK_POS; l2_dispatch_reason
+ * The batched decode of independent sequences (l2_seq_reserve .. l2_read_seq_cache, option key L2_OPT_SEQS) joined the surface without a
+ * version step: it only adds, and a binding detects it by the presence of the l2_seq_reserve symbol. */
 #define L2_ABI_VERSION 5
 
 enum {
@@ -92,9 +94,11 @@ enum {
                                  element instead of the reference's fp64 accumulate (llama2.ts:196-203): faster prompt ingestion, logits within
                                  1e-4 on the fixtures, NOT bit-level parity with the reference (measured exactness);
                                  0 (default): fp64 MFMA, the reference's arithmetic.  Decode is never affected */
-  L2_OPT_CHECK_POS = 10       /* 1 (or L2_CHECK_POS=1 in the environment at creation): l2_forward / l2_prefill refuse (L2_E_STATE) a position that
+  L2_OPT_CHECK_POS = 10,      /* 1 (or L2_CHECK_POS=1 in the environment at creation): l2_forward / l2_prefill refuse (L2_E_STATE) a position that
                                  neither restarts at 0 nor continues the sequence -- the reference's loop feeds pos = 0, 1, 2, ... (llama2.ts:464,
-                                 496) and attention reads whatever rows 0 .. pos - 1 the cache holds; 0 (default): any position is accepted */
+                                 496) and attention reads whatever rows 0 .. pos - 1 the cache holds; 0 (default): any position is accepted.
+                                 Applies per sequence to the batch calls below (sequence 0 shares its position with l2_forward / l2_prefill) */
+  L2_OPT_SEQS = 11            /* read-only: sequences reserved by l2_seq_reserve (0 before it) */
 };
 
 typedef struct l2_ctx l2_ctx;
@@ -200,6 +204,27 @@ int l2_debug_running_sums(int device, const float* values, size_t n, double* sum
  * separate calls would, and returns the logits of the LAST position in logits_out (may be NULL).  Shapes whose
  * dim / hidden_dim are not multiples of 16 fall back to n_tokens l2_forward calls. */
 int l2_prefill(l2_ctx* ctx, const int32_t* tokens, int n_tokens, int pos0, float* logits_out);
+
+/* Batched greedy decode: several independent sequences share every weight read.  The reference's loop decodes one sequence
+ * (llama2.ts:465-508); each row of a batch step is one transformer() call (llama2.ts:205-303) of its own sequence, computed by fp64-MFMA
+ * GEMMs over the rows with prefill's arithmetic (exact products, fp64 accumulation, one fp32 rounding per stored element).
+ * Independent sequences sharing this context's weights.  Sequence 0 is the context's own KV cache (the one l2_forward, l2_prefill and
+ * the device loops use); l2_seq_reserve allocates caches for sequences 1 .. n_seqs-1 ([L][S][d] each) plus the batch buffers.
+ * 1 <= n_seqs <= 64.  Called once per context.  L2_E_CONFIG (with the reason) for shapes the batch path does not cover: tensor
+ * parallel, grouped-query attention honoured, dim or hidden_dim not a multiple of 16; L2_E_HIP (nothing held, the context usable) when
+ * the device memory is not there. */
+int l2_seq_reserve(l2_ctx* ctx, int n_seqs);
+/* l2_prefill into sequence `seq`'s cache (seq 0: exactly l2_prefill). */
+int l2_seq_prefill(l2_ctx* ctx, int seq, const int32_t* tokens, int n_tokens, int pos0, float* logits_out);
+/* One transformer() step for each of n rows: row i feeds tokens[i] at pos[i] of sequence seqs[i] (distinct within a call).
+ * Blocking.  logits_out (may be NULL) receives n x V floats, row i = that sequence's logits.  L2_E_STATE before l2_seq_reserve. */
+int l2_forward_batch(l2_ctx* ctx, int n, const int32_t* seqs, const int32_t* tokens, const int32_t* pos, float* logits_out);
+/* Device-resident greedy loop over n sequences: row i feeds first_tokens[i] at pos0[i], then its own argmax each step
+ * (first maximum, llama2.ts:364-366).  tokens_out is n x steps, row-major per sequence.  Does not stop at BOS.  pos0[i] + steps <= seq_len. */
+int l2_decode_greedy_batch(l2_ctx* ctx, int n, const int32_t* seqs, const int32_t* first_tokens, const int32_t* pos0,
+                           int steps, int32_t* tokens_out);
+/* Read sequence `seq`'s key / value cache (which = L2_S_KEY_CACHE / L2_S_VALUE_CACHE; layer -1 = all), like l2_read_state. */
+int l2_read_seq_cache(l2_ctx* ctx, int seq, int which, int layer, float* out, size_t n_floats);
 
 /* Copy a RunState buffer to the host (parity tests).  For per-layer caches `layer` selects the
  * [S][d] slab (-1: all layers).  After a forward, X holds the final-normed x as in llama2.ts:299.

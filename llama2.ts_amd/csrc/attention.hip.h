@@ -491,6 +491,29 @@ __global__ void __launch_bounds__(64 * NW) pf_attn_tile_kernel(const AttnArgs a,
   attn_tile_dispatch<LR, NW, NT>(b, smem, blockIdx.x, 0, pos0 + p);
 }
 
+// Batched decode (batch.hip.h): grid (head, row).  Row p of the batch is sequence seq[p] at position pos[p]: its query is row p of q, its
+// cache rows 0 .. pos[p] are that sequence's (written by the batch's q / k / v launch before this one), its output row p of xb.
+struct AttnRows {
+  const int* seq;
+  const int* pos;
+  float* const* kc;     // per sequence: key / value cache slabs [L][S][kv_dim]
+  float* const* vc;
+  size_t loff;          // this layer's offset in a slab
+};
+template <int LR, int NW, int NT>
+__global__ void __launch_bounds__(64 * NW) bt_attn_tile_kernel(const AttnArgs a, const AttnRows r) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  AttnArgs b = a;
+  const int p = blockIdx.y, s = r.seq[p];
+  b.q = a.q + (size_t)p * a.dim;
+  b.xb = a.xb + (size_t)p * a.dim;
+  b.kc = Mut<const float>(r.kc[s] + r.loff);
+  b.vc = Mut<const float>(r.vc[s] + r.loff);
+  b.att = Mut<float>(nullptr);
+  b.nsplit = 1;
+  attn_tile_dispatch<LR, NW, NT>(b, smem, blockIdx.x, 0, r.pos[p]);
+}
+
 #ifndef L2_NO_PLAIN_KERNELS
 // Shapes whose head_size or dim is not a multiple of 4 (rows are not 16-byte aligned): one workgroup per head,
 // one thread per timestep, scalar loads.  Correctness only; keeps every rounding of the reference.

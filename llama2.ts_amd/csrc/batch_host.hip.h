@@ -1,0 +1,329 @@
+// batch_host.hip.h -- host side of batched greedy decode (batch.hip.h): l2_seq_reserve, l2_seq_prefill, l2_forward_batch,
+// l2_decode_greedy_batch, l2_read_seq_cache.
+// Part of the one translation unit llama2_hip.hip (included there, in order); not a stand-alone header.
+#pragma once
+
+enum { BT_MAX = 64 };   // rows of a batch step: four 16-row MFMA tiles
+
+// Independent sequences sharing the context's weights.  Sequence 0's caches are the context's own (c->kc / c->vc); the others are
+// allocated by l2_seq_reserve.  The batch step has activations and tables of its own: the single-sequence state (RunState buffers,
+// tokpos, recorded graphs, AQL programs) is never touched by it.
+struct BatchState {
+  int n_seqs = 0;
+  std::vector<float*> kc, vc;             // [n_seqs] cache slabs ([L][S][d] each); entry 0 = the context's own
+  std::vector<int> next_pos;              // L2_OPT_CHECK_POS, sequences 1 ..; sequence 0 uses c->next_pos
+  float** d_kc = nullptr;                 // device copies of kc / vc (the kernels index them by sequence)
+  float** d_vc = nullptr;
+  int* tab = nullptr;                     // device [4][BT_MAX]: sequence, token, position, start position of every row
+  int* h_tab = nullptr;                   // pinned staging of tab
+  int* out = nullptr;                     // device [BT_MAX][S]: tokens picked by row r at position p -> out[r][p - start[r]]
+  float *x = nullptr, *xn = nullptr, *q = nullptr, *xb = nullptr, *hb = nullptr, *logits = nullptr;   // [BT_MAX][d | h | V]
+  hipGraphExec_t g[BT_MAX + 1] = {};      // the recorded step per row count
+  std::vector<uintptr_t> sig;             // what the recorded steps baked in (weight addresses, options)
+  int* seq_of() const { return tab; }
+  int* tok_of() const { return tab + BT_MAX; }
+  int* pos_of() const { return tab + 2 * BT_MAX; }
+  int* start_of() const { return tab + 3 * BT_MAX; }
+};
+
+static void bt_drop_graphs(BatchState* b) {
+  for (auto& g : b->g) if (g) { hipGraphExecDestroy(g); g = nullptr; }
+}
+
+static void batch_free(l2_ctx* c) {
+  BatchState* b = c->bt;
+  if (!b) return;
+  bt_drop_graphs(b);
+  for (size_t s = 1; s < b->kc.size(); ++s) { if (b->kc[s]) hipFree(b->kc[s]); if (b->vc[s]) hipFree(b->vc[s]); }
+  void* dev[] = {b->d_kc, b->d_vc, b->tab, b->out, b->x, b->xn, b->q, b->xb, b->hb, b->logits};
+  for (void* p : dev) if (p) hipFree(p);
+  if (b->h_tab) hipHostFree(b->h_tab);
+  delete b;
+  c->bt = nullptr;
+}
+
+// The shapes the batch path covers: those of the prompt GEMMs (prefill_host.hip.h: can_prefill), named one by one.
+static const char* bt_refusal(const l2_ctx* c) {
+  if (c->tp_path) return "tensor-parallel contexts are not covered by the batch path";
+  if (c->KVH != c->H || c->kvd != c->d) return "grouped-query attention (n_kv_heads < n_heads honoured) is not covered by the batch path";
+  if (c->d % 16) return "dim is not a multiple of 16 (the MFMA tiles of the batch GEMMs)";
+  if (c->h % 16) return "hidden_dim is not a multiple of 16 (the MFMA tiles of the batch GEMMs)";
+  if (!can_prefill(c)) return "head_size is not a multiple of 4 or exceeds 256 (the vector attention kernel)";
+  return nullptr;
+}
+
+extern "C" int l2_seq_reserve(l2_ctx* c, int n_seqs) {
+  if (!c) return fail(L2_E_ARG, "null context");
+  if (n_seqs < 1 || n_seqs > BT_MAX) return fail(L2_E_ARG, "n_seqs %d outside [1, %d]", n_seqs, (int)BT_MAX);
+  if (c->bt) return fail(L2_E_STATE, "l2_seq_reserve was already called on this context (%d sequences)", c->bt->n_seqs);
+  if (const char* why = bt_refusal(c)) return fail(L2_E_CONFIG, "%s", why);
+  HIPCHK(hipSetDevice(c->device));
+  BatchState* b = new BatchState();
+  c->bt = b;
+  b->n_seqs = n_seqs;
+  b->kc.assign(n_seqs, nullptr); b->vc.assign(n_seqs, nullptr); b->next_pos.assign(n_seqs, 0);
+  b->kc[0] = c->kc; b->vc[0] = c->vc;
+  const size_t slab = (size_t)c->L * c->S * c->d * sizeof(float), R = BT_MAX, wide = (size_t)(c->d > c->h ? c->d : c->h);
+  bool ok = true;
+  auto dev = [&](void** p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) ok = false; if (ok) ok = hipMemset(*p, 0, bytes) == hipSuccess; };
+  for (int s = 1; s < n_seqs; ++s) { dev((void**)&b->kc[s], slab); dev((void**)&b->vc[s], slab); }
+  dev((void**)&b->d_kc, R * sizeof(float*)); dev((void**)&b->d_vc, R * sizeof(float*));
+  dev((void**)&b->tab, 4 * R * sizeof(int)); dev((void**)&b->out, R * c->S * sizeof(int));
+  dev((void**)&b->x, R * c->d * 4); dev((void**)&b->xn, R * wide * 4); dev((void**)&b->q, R * c->d * 4);
+  dev((void**)&b->xb, R * c->d * 4); dev((void**)&b->hb, R * c->h * 4); dev((void**)&b->logits, R * c->V * 4);
+  if (ok && hipHostMalloc((void**)&b->h_tab, 4 * R * sizeof(int), 0) != hipSuccess) ok = false;
+  if (ok) {
+    float* tk[BT_MAX] = {}; float* tv[BT_MAX] = {};
+    for (int s = 0; s < n_seqs; ++s) { tk[s] = b->kc[s]; tv[s] = b->vc[s]; }
+    ok = hipMemcpy(b->d_kc, tk, sizeof(tk), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(b->d_vc, tv, sizeof(tv), hipMemcpyHostToDevice) == hipSuccess;
+  }
+  if (!ok) {
+    const hipError_t e = hipGetLastError();
+    batch_free(c);
+    return fail(L2_E_HIP, "l2_seq_reserve: device memory for %d sequences: %s", n_seqs, hipGetErrorString(e));
+  }
+  return L2_OK;
+}
+
+// Arguments of a batch call, all checked before anything touches the GPU.
+static int bt_check(l2_ctx* c, int n, const int32_t* seqs, const int32_t* tokens, const int32_t* pos, int steps) {
+  if (!c) return fail(L2_E_ARG, "null context");
+  if (!seqs || !tokens || !pos) return fail(L2_E_ARG, "null argument");
+  if (!c->bt) return fail(L2_E_STATE, "no sequences reserved: call l2_seq_reserve first");
+  const BatchState* b = c->bt;
+  if (n < 1 || n > b->n_seqs) return fail(L2_E_ARG, "n = %d outside [1, n_seqs = %d]", n, b->n_seqs);
+  if (steps < 0) return fail(L2_E_ARG, "steps %d < 0", steps);
+  bool seen[BT_MAX] = {};
+  for (int i = 0; i < n; ++i) {
+    const int s = seqs[i];
+    if (s < 0 || s >= b->n_seqs) return fail(L2_E_ARG, "row %d: sequence %d outside [0, n_seqs = %d)", i, s, b->n_seqs);
+    if (seen[s]) return fail(L2_E_ARG, "row %d: sequence %d appears twice in one call", i, s);
+    seen[s] = true;
+    if (tokens[i] < 0 || tokens[i] >= c->V) return fail(L2_E_ARG, "row %d: token %d outside [0, vocab_size=%d)", i, tokens[i], c->V);
+    if (pos[i] < 0 || pos[i] >= c->S) return fail(L2_E_ARG, "row %d: pos %d outside [0, seq_len=%d)", i, pos[i], c->S);
+    if (pos[i] + (steps > 0 ? steps : 1) > c->S) return fail(L2_E_ARG, "row %d: pos %d + steps %d runs past seq_len=%d", i, pos[i], steps, c->S);
+    const int next = s == 0 ? c->next_pos : b->next_pos[s];
+    if (c->opt_pos_check && pos[i] != 0 && pos[i] > next)
+      return fail(L2_E_STATE, "L2_CHECK_POS: sequence %d, pos %d skips ahead of the sequence (cache rows 0 .. %d have been written)", s, pos[i], next - 1);
+  }
+  return L2_OK;
+}
+
+static void bt_set_next(l2_ctx* c, int s, int next) { if (s == 0) c->next_pos = next; else c->bt->next_pos[s] = next; }
+
+// Weights of the batch classifier: the row-major matrix (wcls, or the embedding table when shared), or -- once wcls has been given back
+// -- the decode classifier's repacked copy.
+static void bt_cls_weights(const l2_ctx* c, PfArgs& a) {
+  a.w0 = a.w1 = a.w2 = nullptr; a.wp = nullptr; a.pk_wstride = 0; a.pk_groups = 0;
+  if (!c->shared && c->released[L2_T_WCLS]) {
+    const l2_ctx::Packed& p = c->packed[MODE_CLS];
+    a.wp = p.buf; a.pk_wstride = p.grid * p.nwaves; a.pk_groups = (int)(p.layer_elems / (2 * (size_t)c->d));
+    return;
+  }
+  a.w0 = c->w[L2_T_WCLS];
+}
+
+// One batch GEMM: the register-blocked form where prefill takes it for one 64-row chunk, else one 16-row weight tile per workgroup.
+template <int MODE>
+static void bt_gemm(const l2_ctx* c, const PfArgs& a, int tt, hipStream_t st) {
+  if constexpr (MODE == MODE_WO || MODE == MODE_W13 || MODE == MODE_W2) {
+    if (pf3_ok(c) && tt == 4) { launch_pf3<MODE, 1>(a, 1, st); return; }
+  }
+  const dim3 grid((a.rows + 15) / 16);
+  if (tt == 4) hipLaunchKernelGGL((pf_gemm_kernel<MODE, 4, 4>), grid, dim3(256), 0, st, a);
+  else if (tt == 2) hipLaunchKernelGGL((pf_gemm_kernel<MODE, 4, 2>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((pf_gemm_kernel<MODE, 4, 1>), grid, dim3(256), 0, st, a);
+}
+
+static hipError_t launch_bt_attn(const l2_ctx* c, const AttnArgs& a, const AttnRows& r, int n, hipStream_t st) {
+  const int lr = attn_lr(c->hs), nw = attn_nw(c);
+  const size_t lds = attn_tile_lds(c->S, 1, nw, nw == 8 ? 8 : 16);
+  const dim3 grid(c->H, n), block(64 * nw);
+#define L2_BT(LR, NW, NT) do { hipError_t e_ = lds_opt_in(&bt_attn_tile_kernel<LR, NW, NT>, lds); if (e_ != hipSuccess) return e_; \
+                               hipLaunchKernelGGL((bt_attn_tile_kernel<LR, NW, NT>), grid, block, lds, st, a, r); } while (0)
+  switch (lr) {      // the instances launch_attn_tile uses
+    case 4: L2_BT(4, 4, 16); break;
+    case 8: L2_BT(8, 4, 16); break;
+    case 16: L2_BT(16, 4, 16); break;
+    case 32: L2_BT(32, 8, 8); break;
+    default: L2_BT(64, 4, 16); break;
+  }
+#undef L2_BT
+  return hipGetLastError();
+}
+
+// One batch step of n rows (tables already on the device): embed, the layers, final norm, classifier, per-row pick.
+static int bt_enqueue(l2_ctx* c, int n, hipStream_t st) {
+  BatchState* b = c->bt;
+  const int tt = (n > 32) ? 4 : (n > 16) ? 2 : 1, nt = 16 * tt;      // token rows the kernels see (whole 16-row MFMA tiles)
+  const size_t d = c->d;
+  hipLaunchKernelGGL(pf_embed_kernel, dim3(nt), dim3(256), 0, st, b->x, c->w[L2_T_TOKEN_EMBEDDING], (const int*)b->tok_of(), c->d, n);
+  LCHK(hipGetLastError());
+  for (int l = 0; l < c->L; ++l) {
+    const size_t loff = (size_t)l * c->S * c->d;
+    PfArgs a;
+    memset(&a, 0, sizeof(a));
+    a.fr = c->w[L2_T_FREQ_REAL]; a.fi = c->w[L2_T_FREQ_IMAG]; a.head_size = c->hs; a.dim = c->d; a.pos0 = 0; a.nvalid = n;
+    a.x = b->x;
+    a.row_seq = b->seq_of(); a.row_pos = b->pos_of(); a.seq_kc = b->d_kc; a.seq_vc = b->d_vc; a.seq_loff = loff;
+    // rmsnorm + q,k,v + RoPE + every row's cache row (llama2.ts:216-240)
+    hipLaunchKernelGGL(pf_norm_kernel, dim3(nt), dim3(256), 0, st, b->xn, b->x, c->w[L2_T_RMS_ATT] + d * l, c->d);
+    pf_weights<MODE_QKV>(c, l, a, L2_T_WQ, L2_T_WK, L2_T_WV);
+    a.xin = b->xn; a.out = b->q; a.n = c->d; a.rows = 3 * c->d;
+    bt_gemm<MODE_QKV_ROWS>(c, a, tt, st);
+    LCHK(hipGetLastError());
+    // attention, one workgroup per (head, row) over the row's own cache (llama2.ts:244-267)
+    AttnArgs aa;
+    fill_attn_args(c, l, aa);      // (its split count is the single-sequence step's: the kernel runs one workgroup per (head, row))
+    aa.q = b->q; aa.xb = b->xb; aa.att = nullptr; aa.tokpos = nullptr; aa.part = nullptr; aa.counter = nullptr;
+    AttnRows ar = {b->seq_of(), b->pos_of(), b->d_kc, b->d_vc, loff};
+    LCHK(launch_bt_attn(c, aa, ar, n, st));
+    // wo + residual (llama2.ts:270-273)
+    pf_weights<MODE_WO>(c, l, a, L2_T_WO, -1, -1); a.xin = b->xb; a.n = c->d; a.rows = c->d;
+    bt_gemm<MODE_WO>(c, a, tt, st);
+    // rmsnorm + w1,w3 + SwiGLU (llama2.ts:276-289)
+    hipLaunchKernelGGL(pf_norm_kernel, dim3(nt), dim3(256), 0, st, b->xn, b->x, c->w[L2_T_RMS_FFN] + d * l, c->d);
+    pf_weights<MODE_W13>(c, l, a, L2_T_W1, L2_T_W3, -1);
+    a.xin = b->xn; a.out = b->hb; a.n = c->d; a.rows = c->h;
+    bt_gemm<MODE_W13>(c, a, tt, st);
+    // w2 + residual (llama2.ts:292-295)
+    pf_weights<MODE_W2>(c, l, a, L2_T_W2, -1, -1); a.xin = b->hb; a.n = c->h; a.rows = c->d;
+    bt_gemm<MODE_W2>(c, a, tt, st);
+    LCHK(hipGetLastError());
+  }
+  // final rmsnorm + classifier (llama2.ts:299-302): logits [row][V]
+  hipLaunchKernelGGL(pf_norm_kernel, dim3(nt), dim3(256), 0, st, b->xn, b->x, c->w[L2_T_RMS_FINAL], c->d);
+  PfArgs a;
+  memset(&a, 0, sizeof(a));
+  bt_cls_weights(c, a);
+  a.xin = b->xn; a.out = b->logits; a.n = c->d; a.rows = c->V; a.dim = c->d; a.nvalid = n;
+  bt_gemm<MODE_CLS_ROWS>(c, a, tt, st);
+  // every row's pick (llama2.ts:364-366), fed next
+  hipLaunchKernelGGL(bt_argmax_kernel, dim3(n), dim3(1024), 0, st, (const float*)b->logits, c->V, b->tok_of(), b->pos_of(), (const int*)b->start_of(), b->out, c->S);
+  LCHK(hipGetLastError());
+  return L2_OK;
+}
+
+// What a recorded step baked in: every weight address it may read and the options that shape it.  A change drops the recordings.
+static std::vector<uintptr_t> bt_signature(const l2_ctx* c) {
+  std::vector<uintptr_t> s;
+  for (int k = 0; k < L2_T_COUNT; ++k) { s.push_back((uintptr_t)c->w[k]); s.push_back(c->released[k]); }
+  for (const auto& p : c->packed) { s.push_back((uintptr_t)p.buf); s.push_back((uintptr_t)p.grid); s.push_back((uintptr_t)p.nwaves); }
+  s.push_back((uintptr_t)c->opt_exact);
+  return s;
+}
+
+// Upload the tables of n rows and run `steps` batch steps (recorded once per row count, replayed; eager with L2_OPT_USE_GRAPH = 0).
+static int bt_run(l2_ctx* c, int n, const int32_t* seqs, const int32_t* tokens, const int32_t* pos, int steps) {
+  BatchState* b = c->bt;
+  int rc = ensure_ready(c);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  const std::vector<uintptr_t> sig = bt_signature(c);
+  if (sig != b->sig) { bt_drop_graphs(b); b->sig = sig; }
+  HIPCHK(hipStreamSynchronize(c->stream));      // (h_tab: the previous call's copy has completed)
+  for (int i = 0; i < BT_MAX; ++i) {
+    const bool live = i < n;
+    b->h_tab[i] = live ? seqs[i] : 0;
+    b->h_tab[BT_MAX + i] = live ? tokens[i] : 0;
+    b->h_tab[2 * BT_MAX + i] = live ? pos[i] : 0;
+    b->h_tab[3 * BT_MAX + i] = live ? pos[i] : 0;
+  }
+  HIPCHK(hipMemcpyAsync(b->tab, b->h_tab, 4 * BT_MAX * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (c->opt_graph && !b->g[n]) {
+    hipGraph_t graph = nullptr;
+    LCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    rc = bt_enqueue(c, n, c->stream);
+    const hipError_t e = hipStreamEndCapture(c->stream, &graph);
+    if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
+    if (e != hipSuccess) return fail(L2_E_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+    const hipError_t e2 = hipGraphInstantiate(&b->g[n], graph, nullptr, nullptr, 0);
+    hipGraphDestroy(graph);
+    if (e2 != hipSuccess) { b->g[n] = nullptr; return fail(L2_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e2)); }
+  }
+  for (int s = 0; s < steps; ++s) {
+    if (c->opt_graph) HIPCHK(hipGraphLaunch(b->g[n], c->stream));
+    else { rc = bt_enqueue(c, n, c->stream); if (rc) return rc; }
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int i = 0; i < n; ++i) bt_set_next(c, seqs[i], pos[i] + steps);
+  return L2_OK;
+}
+
+extern "C" int l2_forward_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_t* tokens, const int32_t* pos, float* logits_out) {
+  int rc = bt_check(c, n, seqs, tokens, pos, 1);
+  if (rc) return rc;
+  rc = bt_run(c, n, seqs, tokens, pos, 1);
+  if (rc) return rc;
+  if (logits_out) HIPCHK(hipMemcpy(logits_out, c->bt->logits, (size_t)n * c->V * sizeof(float), hipMemcpyDeviceToHost));
+  return L2_OK;
+}
+
+extern "C" int l2_decode_greedy_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_t* first_tokens, const int32_t* pos0, int steps,
+                                      int32_t* tokens_out) {
+  int rc = bt_check(c, n, seqs, first_tokens, pos0, steps);
+  if (rc) return rc;
+  if (!tokens_out && steps > 0) return fail(L2_E_ARG, "null tokens_out");
+  if (steps == 0) return L2_OK;
+  rc = bt_run(c, n, seqs, first_tokens, pos0, steps);
+  if (rc) return rc;
+  HIPCHK(hipMemcpy2D(tokens_out, (size_t)steps * sizeof(int32_t), c->bt->out, (size_t)c->S * sizeof(int), (size_t)steps * sizeof(int32_t), n, hipMemcpyDeviceToHost));
+  return L2_OK;
+}
+
+extern "C" int l2_seq_prefill(l2_ctx* c, int seq, const int32_t* tokens, int n_tokens, int pos0, float* logits_out) {
+  if (!c || !tokens) return fail(L2_E_ARG, "null argument");
+  if (!c->bt) return fail(L2_E_STATE, "no sequences reserved: call l2_seq_reserve first");
+  BatchState* b = c->bt;
+  if (seq < 0 || seq >= b->n_seqs) return fail(L2_E_ARG, "sequence %d outside [0, n_seqs = %d)", seq, b->n_seqs);
+  if (seq == 0) return l2_prefill(c, tokens, n_tokens, pos0, logits_out);
+  if (n_tokens <= 0 || pos0 < 0 || pos0 + n_tokens > c->S) return fail(L2_E_ARG, "positions %d..%d outside [0, seq_len=%d)", pos0, pos0 + n_tokens - 1, c->S);
+  for (int i = 0; i < n_tokens; ++i) if (tokens[i] < 0 || tokens[i] >= c->V) return fail(L2_E_ARG, "token %d outside [0, vocab_size=%d)", tokens[i], c->V);
+  if (c->opt_pos_check && pos0 != 0 && pos0 > b->next_pos[seq])
+    return fail(L2_E_STATE, "L2_CHECK_POS: sequence %d, pos %d skips ahead of the sequence (cache rows 0 .. %d have been written)", seq, pos0, b->next_pos[seq] - 1);
+  if (n_tokens == 1) {      // one row: the batch step
+    const int32_t s1[1] = {seq}, t1[1] = {tokens[0]}, p1[1] = {pos0};
+    return l2_forward_batch(c, 1, s1, t1, p1, logits_out);
+  }
+  int rc = ensure_ready(c);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  const int step = pf3_ok(c) ? PF_S * PF_T : PF_T;
+  int done = 0;
+  while (done < n_tokens) {
+    const int n = (n_tokens - done < step) ? n_tokens - done : step;
+    rc = prefill_chunk(c, tokens + done, n, pos0 + done, b->kc[seq], b->vc[seq]);
+    if (rc) return rc;
+    done += n;
+  }
+  if (pos0 + n_tokens > b->next_pos[seq] || pos0 == 0) b->next_pos[seq] = pos0 + n_tokens;
+  if (logits_out) {      // the last position's logits: final norm of its row and the batch classifier (the context's own buffers stay as they are)
+    const int last = (n_tokens - 1) % step;
+    hipLaunchKernelGGL(pf_norm_kernel, dim3(1), dim3(256), 0, c->stream, b->xn, (const float*)(c->pf_x + (size_t)last * c->d), c->w[L2_T_RMS_FINAL], c->d);
+    PfArgs a;
+    memset(&a, 0, sizeof(a));
+    bt_cls_weights(c, a);
+    a.xin = b->xn; a.out = b->logits; a.n = c->d; a.rows = c->V; a.dim = c->d; a.nvalid = 1;
+    bt_gemm<MODE_CLS_ROWS>(c, a, 1, c->stream);
+    LCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(logits_out, b->logits, (size_t)c->V * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return L2_OK;
+}
+
+extern "C" int l2_read_seq_cache(l2_ctx* c, int seq, int which, int layer, float* out, size_t n_floats) {
+  if (!c || !out) return fail(L2_E_ARG, "null argument");
+  if (!c->bt) return fail(L2_E_STATE, "no sequences reserved: call l2_seq_reserve first");
+  const BatchState* b = c->bt;
+  if (seq < 0 || seq >= b->n_seqs) return fail(L2_E_ARG, "sequence %d outside [0, n_seqs = %d)", seq, b->n_seqs);
+  if (which != L2_S_KEY_CACHE && which != L2_S_VALUE_CACHE) return fail(L2_E_ARG, "state %d is not a cache (L2_S_KEY_CACHE / L2_S_VALUE_CACHE)", which);
+  if (layer < -1 || layer >= c->L) return fail(L2_E_ARG, "layer %d out of range", layer);
+  const size_t slab = (size_t)c->S * c->d, n = layer < 0 ? slab * c->L : slab;
+  if (n_floats != n) return fail(L2_E_ARG, "cache has %zu floats, caller asked for %zu", n, n_floats);
+  const float* src = (which == L2_S_KEY_CACHE ? b->kc[seq] : b->vc[seq]) + (layer < 0 ? 0 : slab * layer);
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  HIPCHK(hipMemcpy(out, src, n * sizeof(float), hipMemcpyDeviceToHost));
+  return L2_OK;
+}

@@ -118,6 +118,7 @@ struct P2PArgs {
 };
 
 // ------------------------------------------------------------------------------------------------
+struct BatchState;                   // batched decode of independent sequences (batch_host.hip.h)
 struct l2_ctx {
   int32_t hdr[7];
   int d, h, L, H, V, S, hs;
@@ -240,7 +241,9 @@ struct l2_ctx {
   bool released[L2_T_COUNT] = {};
   bool rerelease = false;           // l2_read_tensor brought the row-major tensors back for a parity read: the next step gives them away again (no repack)
   int opt_one_copy = 1;             // L2_ONE_COPY=0: keep both copies (A/B, development switch)
+  BatchState* bt = nullptr;         // l2_seq_reserve: the other sequences' caches, the batch step's buffers and recorded steps
 };
+static void batch_free(l2_ctx* c);
 
 static bool is_layered(int kind) { return kind >= L2_T_RMS_ATT && kind <= L2_T_W3; }
 

@@ -31,6 +31,7 @@
 #include "kernels.hip.h"
 #include "attention_inst.hip.h"      // attention.hip.h + its instances as extern templates (compiled in attention_inst.hip)
 #include "prefill.hip.h"
+#include "batch.hip.h"
 #include "sampler.h"
 #include "aql_queue.h"
 
@@ -98,6 +99,7 @@ extern "C" void l2_destroy(l2_ctx* c) {
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
   destroy_graphs(c);
+  batch_free(c);
   if (c->aql) { aql_destroy(c->aql); c->aql = nullptr; }
   if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
   if (c->loop_tmp) hipFree(c->loop_tmp);
@@ -967,6 +969,7 @@ extern "C" int l2_forward(l2_ctx* c, int token, int pos, float* logits_out) {
 extern "C" float* l2_logits_host(l2_ctx* c) { return c ? c->h_logits : nullptr; }
 
 #include "prefill_host.hip.h"
+#include "batch_host.hip.h"
 
 static int run_greedy(l2_ctx* c, int first_token, int pos0, int steps, bool timed, float* ms) {
   if (!c) return fail(L2_E_ARG, "null context");
@@ -1149,7 +1152,7 @@ extern "C" int l2_set_option(l2_ctx* c, int key, int value) {
     case L2_OPT_AQL_QUEUE: c->opt_aql = !!value; if (value) c->aql_tried = false; return L2_OK;
     case L2_OPT_PREFILL_F32_MFMA: c->opt_pf_f32 = !!value; return L2_OK;
     case L2_OPT_CHECK_POS: c->opt_pos_check = !!value; return L2_OK;
-    case L2_OPT_PACKED_MIB: case L2_OPT_WEIGHT_MIB: case L2_OPT_SAMPLED_TOKENS: case L2_OPT_SAMPLED_SERIAL:
+    case L2_OPT_PACKED_MIB: case L2_OPT_WEIGHT_MIB: case L2_OPT_SAMPLED_TOKENS: case L2_OPT_SAMPLED_SERIAL: case L2_OPT_SEQS:
       return fail(L2_E_ARG, "option %d is read-only", key);
     default: return fail(L2_E_ARG, "unknown option %d", key);
   }
@@ -1164,6 +1167,7 @@ extern "C" int l2_get_option(l2_ctx* c, int key, int* value) {
     case L2_OPT_AQL_QUEUE: *value = aql_usable(c) ? 1 : 0; return L2_OK;      // (why not: l2_dispatch_reason -- l2_last_error is for failures)
     case L2_OPT_PREFILL_F32_MFMA: *value = c->opt_pf_f32; return L2_OK;
     case L2_OPT_CHECK_POS: *value = c->opt_pos_check; return L2_OK;
+    case L2_OPT_SEQS: *value = c->bt ? c->bt->n_seqs : 0; return L2_OK;
     case L2_OPT_PACKED_MIB: {
       size_t floats = 0;
       if (c->packed_valid) for (int m = 0; m < 5; ++m) if (c->packed[m].buf) floats += c->packed[m].layer_elems * (size_t)(m == MODE_CLS ? 1 : c->L);

@@ -22,6 +22,10 @@ namespace l2k {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
+// GEMM modes of the batched decode step only (batch.hip.h), behind kernels.hip.h's MODE_*: q / k / v whose epilogue takes every row's
+// position and cache from device tables, and the classifier over any number of rows (the last tile's rows clamped, its stores masked)
+enum { MODE_QKV_ROWS = 5, MODE_CLS_ROWS = 6 };
+
 enum { PF_T = 64, PF_S = 4 };   // tokens per chunk: one, two or four MFMA tiles of 16; chunks per launch of the register-blocked GEMMs (blockIdx.y)
 
 struct PfArgs {
@@ -40,6 +44,13 @@ struct PfArgs {
   const float* wp;     // [round][column batch][place in the round][row of the group][u][lane] float4 of this layer, or null
   int pk_wstride;      // row groups per round (waves of the decode launch's grid)
   int pk_groups;       // row groups of the phase (2 rows each; w1 / w3: row g of both)
+  // Batched decode (batch.hip.h), read by the MODE_*_ROWS instances only: row t is sequence row_seq[t] at position row_pos[t], whose
+  // cache slabs of this layer start at seq_kc[s] / seq_vc[s] + seq_loff
+  const int* row_seq;
+  const int* row_pos;
+  float* const* seq_kc;
+  float* const* seq_vc;
+  size_t seq_loff;
 };
 
 // Where float4 `c4` of row `r` of row group `g` lies in the repacked copy, split into the part that depends on the lane's row only
@@ -128,6 +139,26 @@ __device__ __forceinline__ void pf_emit(const PfArgs& a, const V& av, const V& a
       const double v = h1;
       const float sl = (float)(v * (1.0 / (1.0 + exp(-v))));          // llama2.ts:285
       a.out[(size_t)t * a.rows + i] = (float)((double)sl * (double)h3);  // llama2.ts:289
+    } else if (MODE == MODE_QKV_ROWS) {
+      // batched decode: row t is its own sequence at its own position (llama2.ts:224-240 per row); rows past nvalid store nothing
+      const bool live = t < a.nvalid;
+      const int pos = live ? a.row_pos[t] : 0;
+      const size_t at = (size_t)pos * a.dim + i;
+      if (m == 2) {
+        if (live) (a.seq_vc[a.row_seq[t]] + a.seq_loff)[at] = sv;
+      } else {
+        const float other = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sv), 0xB1, 0xf, 0xf, false));   // (every lane)
+        const float s0 = (j & 1) ? other : sv, s1 = (j & 1) ? sv : other;
+        const int idx = pos * (a.head_size / 2) + (i % a.head_size) / 2;
+        const double fcr = a.fr[idx], fci = a.fi[idx];
+        const float o = (j & 1) ? (float)((double)s0 * fci + (double)s1 * fcr) : (float)((double)s0 * fcr - (double)s1 * fci);
+        if (live) {
+          if (m == 0) a.out[(size_t)t * a.dim + i] = o;
+          else (a.seq_kc[a.row_seq[t]] + a.seq_loff)[at] = o;
+        }
+      }
+    } else if (MODE == MODE_CLS_ROWS) {   // logits [rows of the batch][vocab] (llama2.ts:302)
+      if (t < a.nvalid && i < a.rows) a.out[(size_t)t * a.rows + i] = sv;
     } else {   // WO / W2: residual accum (llama2.ts:273, 295)
       float* xp = a.x + (size_t)t * a.dim + i;
       *xp = *xp + sv;
@@ -213,16 +244,17 @@ __global__ void __launch_bounds__(64 * NW) pf_gemm_kernel(const PfArgs a) {
   const int row0 = blockIdx.x * 16;
   int m = 0, i0 = row0;
   const float* wbase = a.w0;
-  if (MODE == MODE_QKV) { m = row0 / a.dim; i0 = row0 - m * a.dim; wbase = (m == 0) ? a.w0 : (m == 1) ? a.w1 : a.w2; }
+  if (MODE == MODE_QKV || MODE == MODE_QKV_ROWS) { m = row0 / a.dim; i0 = row0 - m * a.dim; wbase = (m == 0) ? a.w0 : (m == 1) ? a.w1 : a.w2; }
   const int j = lane & 15, kq = lane >> 4;
+  const int jr = (MODE == MODE_CLS_ROWS) ? min(row0 + j, a.rows - 1) - row0 : j;     // the lane's weight row (clamped past the classifier's last)
   const bool pk = a.wp != nullptr;
-  const float* wrow = pk ? nullptr : wbase + (size_t)(i0 + j) * n + 4 * kq;
-  const float* wrow3 = (DUAL && !pk) ? a.w1 + (size_t)(i0 + j) * n + 4 * kq : nullptr;
+  const float* wrow = pk ? nullptr : wbase + (size_t)(i0 + jr) * n + 4 * kq;
+  const float* wrow3 = (DUAL && !pk) ? a.w1 + (size_t)(i0 + jr) * n + 4 * kq : nullptr;
   PkLane pl = {0, 0, 0}, pl3 = {0, 0, 0};
   if (pk) {
     int g, r;
-    pk_group_of<MODE>(row0 + j, false, g, r); pl = pk_lane(a, g, r);
-    if (DUAL) { pk_group_of<MODE>(row0 + j, true, g, r); pl3 = pk_lane(a, g, r); }
+    pk_group_of<MODE>(row0 + jr, false, g, r); pl = pk_lane(a, g, r);
+    if (DUAL) { pk_group_of<MODE>(row0 + jr, true, g, r); pl3 = pk_lane(a, g, r); }
   }
   const int pk_lastci = (((n >> 2) + 127) >> 7) - 1;
   const f4* wp4 = reinterpret_cast<const f4*>(a.wp);

@@ -77,8 +77,9 @@ static void pf_weights(const l2_ctx* c, int l, PfArgs& a, int k0, int k1, int k2
   if (k2 >= 0) a.w2 = c->w[k2] + c->layer_elems[k2] * l;
 }
 
-// One launch sequence for up to PF_S chunks of PF_T prompt positions (n tokens at pos0 ...): every GEMM sees all of them.
-static int prefill_chunk(l2_ctx* c, const int32_t* tokens, int n, int pos0) {
+// One launch sequence for up to PF_S chunks of PF_T prompt positions (n tokens at pos0 ...): every GEMM sees all of them.  `kc` / `vc`: the
+// sequence's cache slabs ([L][S][d]; l2_prefill: the context's own, l2_seq_prefill: a reserved sequence's).
+static int prefill_chunk(l2_ctx* c, const int32_t* tokens, int n, int pos0, float* kc, float* vc) {
   hipStream_t st = c->stream;
   const size_t d = c->d, h = c->h;
   constexpr size_t ROWS = (size_t)PF_S * PF_T;
@@ -105,7 +106,7 @@ static int prefill_chunk(l2_ctx* c, const int32_t* tokens, int n, int pos0) {
     // rmsnorm + q,k,v + RoPE + cache rows (llama2.ts:216-240)
     hipLaunchKernelGGL(pf_norm_kernel, dim3(nt), dim3(256), 0, st, c->pf_xn, c->pf_x, c->w[L2_T_RMS_ATT] + d * l, c->d);
     pf_weights<MODE_QKV>(c, l, a, L2_T_WQ, L2_T_WK, L2_T_WV);
-    a.xin = c->pf_xn; a.out = c->pf_q; a.kc = c->kc + loff; a.vc = c->vc + loff; a.n = c->d; a.rows = 3 * c->d;
+    a.xin = c->pf_xn; a.out = c->pf_q; a.kc = kc + loff; a.vc = vc + loff; a.n = c->d; a.rows = 3 * c->d;
     launch_pf_gemm<MODE_QKV>(c, a, 4, tt, chunks, st);
     LCHK(hipGetLastError());
     // attention, one workgroup per (head, query) (llama2.ts:244-267)
@@ -113,7 +114,7 @@ static int prefill_chunk(l2_ctx* c, const int32_t* tokens, int n, int pos0) {
     if (c->pf_attn && !c->opt_exact && (c->hs == 64 || c->hs == 128) && alds <= 150 * 1024) {
       // 16 queries per workgroup on the fp64 MFMA (prefill.hip.h: pf_attn_mfma_kernel)
       PfAttnArgs pa;
-      pa.q = c->pf_q; pa.kc = c->kc + loff; pa.vc = c->vc + loff; pa.xb = c->pf_xb;
+      pa.q = c->pf_q; pa.kc = kc + loff; pa.vc = vc + loff; pa.xb = c->pf_xb;
       pa.dim = c->d; pa.head_size = c->hs; pa.seq_len = c->S; pa.pos0 = pos0; pa.nvalid = n;
       pa.inv_sqrt_hs = 1.0 / sqrt((double)c->hs);
       const dim3 grid(c->H, (n + 15) / 16);
@@ -129,7 +130,7 @@ static int prefill_chunk(l2_ctx* c, const int32_t* tokens, int n, int pos0) {
       AttnArgs aa;
       c->cur_splits = 1; c->cur_fused = false;
       fill_attn_args(c, l, aa);
-      aa.q = c->pf_q; aa.xb = c->pf_xb; aa.att = nullptr; aa.pos_plus1 = 1;
+      aa.q = c->pf_q; aa.xb = c->pf_xb; aa.att = nullptr; aa.pos_plus1 = 1; aa.kc = kc + loff; aa.vc = vc + loff;
       LCHK(launch_attn_tile(c, aa, n, pos0, st));
     }
     // wo + residual (llama2.ts:270-273)
@@ -167,7 +168,7 @@ extern "C" int l2_prefill(l2_ctx* c, const int32_t* tokens, int n_tokens, int po
   int done = 0;
   while (done < n_tokens) {
     const int n = (n_tokens - done < step) ? n_tokens - done : step;
-    rc = prefill_chunk(c, tokens + done, n, pos0 + done);
+    rc = prefill_chunk(c, tokens + done, n, pos0 + done, c->kc, c->vc);
     if (rc) return rc;
     done += n;
   }

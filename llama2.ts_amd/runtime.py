@@ -26,6 +26,7 @@ S_X, S_XB, S_XB2, S_HB, S_HB2, S_Q, S_K, S_V, S_ATT, S_LOGITS, S_KEY_CACHE, S_VA
 STATE_IDS = dict(x=S_X, xb=S_XB, xb2=S_XB2, hb=S_HB, hb2=S_HB2, q=S_Q, k=S_K, v=S_V, att=S_ATT, logits=S_LOGITS,
                  key_cache=S_KEY_CACHE, value_cache=S_VALUE_CACHE)
 OPT_EXACT_ATTENTION, OPT_USE_GRAPH, OPT_KEEP_STATE, OPT_PACKED_MIB, OPT_WEIGHT_MIB, OPT_SAMPLED_TOKENS, OPT_SAMPLED_SERIAL, OPT_AQL_QUEUE, OPT_PREFILL_F32_MFMA, OPT_CHECK_POS = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
+OPT_SEQS = 11      # read-only: sequences reserved by seq_reserve (0 before it)
 F_GQA, F_GENERATE_ROPE = 1, 2     # l2_create_ex flags
 TP_SOLO_ID = b"L2-SOLO-SHARD-TIMING"   # l2_create_tp id of a shard-timing context (include/llama2_hip.h: L2_TP_SOLO_ID)
 
@@ -33,7 +34,8 @@ TP_SOLO_ID = b"L2-SOLO-SHARD-TIMING"   # l2_create_tp id of a shard-timing conte
 ABI_SYMBOLS = ["l2_abi_version", "l2_device_count", "l2_last_error", "l2_create", "l2_destroy", "l2_tp_unique_id",
                "l2_create_tp", "l2_upload", "l2_synth_fill", "l2_read_tensor", "l2_forward", "l2_logits_host",
                "l2_decode_greedy", "l2_decode_sample", "l2_debug_running_sums", "l2_read_state", "l2_set_option", "l2_get_option", "l2_timer_start",
-               "l2_timer_stop", "l2_bench_gemv", "l2_bench_decode", "l2_load_checkpoint", "l2_get_header", "l2_prefill", "l2_bench_dominant_in_situ", "l2_tp_mode", "l2_create_ex", "l2_bench_tokens", "l2_dispatch_reason"]
+               "l2_timer_stop", "l2_bench_gemv", "l2_bench_decode", "l2_load_checkpoint", "l2_get_header", "l2_prefill", "l2_bench_dominant_in_situ", "l2_tp_mode", "l2_create_ex", "l2_bench_tokens", "l2_dispatch_reason",
+               "l2_seq_reserve", "l2_seq_prefill", "l2_forward_batch", "l2_decode_greedy_batch", "l2_read_seq_cache"]
 
 
 class L2Error(RuntimeError):
@@ -88,6 +90,11 @@ def lib():
     L.l2_bench_tokens.argtypes = [vp, vp, i32]
     L.l2_dispatch_reason.argtypes = [vp]
     L.l2_dispatch_reason.restype = C.c_char_p
+    L.l2_seq_reserve.argtypes = [vp, i32]
+    L.l2_seq_prefill.argtypes = [vp, i32, vp, i32, i32, vp]
+    L.l2_forward_batch.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.l2_decode_greedy_batch.argtypes = [vp, i32, vp, vp, vp, i32, vp]
+    L.l2_read_seq_cache.argtypes = [vp, i32, i32, i32, vp, sz]
     for name in ABI_SYMBOLS:   # fail at load time, not at first use, if the .so is stale
         getattr(L, name)
     _lib = L
@@ -227,6 +234,47 @@ class Context:
         _check(lib().l2_decode_sample(self._h, int(first_token), int(pos0), int(steps), float(temperature), float(topp),
                                       C.byref(st), out.ctypes.data))
         return out, int(st.value)
+
+    # -- independent sequences over this context's weights (batched greedy decode)
+    def seq_reserve(self, n):
+        """Reserve n sequences (1..64): sequence 0 is this context's own cache, 1..n-1 get caches of their own."""
+        _check(lib().l2_seq_reserve(self._h, int(n)))
+
+    def seq_prefill(self, seq, tokens, pos0=0):
+        """Feed a run of tokens into sequence `seq` at pos0..; returns the logits of the last position."""
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        out = np.empty(self.cfg.vocab_size, dtype=np.float32)
+        _check(lib().l2_seq_prefill(self._h, int(seq), t.ctypes.data, t.size, int(pos0), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def _rows(*cols):
+        arrs = [np.ascontiguousarray(c, dtype=np.int32).reshape(-1) for c in cols]
+        if len({a.size for a in arrs}) != 1:
+            raise ValueError("sequence, token and position lists must have one entry per row")
+        return arrs
+
+    def forward_batch(self, seqs, tokens, pos):
+        """One transformer() step per row: row i feeds tokens[i] at pos[i] of sequence seqs[i]; returns the (n, V) logits."""
+        s, t, p = self._rows(seqs, tokens, pos)
+        out = np.empty((s.size, self.cfg.vocab_size), dtype=np.float32)
+        _check(lib().l2_forward_batch(self._h, s.size, s.ctypes.data, t.ctypes.data, p.ctypes.data, out.ctypes.data))
+        return out
+
+    def decode_greedy_batch(self, seqs, first_tokens, pos0, steps):
+        """Device-resident greedy loop over the rows; returns the (n, steps) picked tokens."""
+        s, t, p = self._rows(seqs, first_tokens, pos0)
+        out = np.zeros((s.size, int(steps)), dtype=np.int32)
+        _check(lib().l2_decode_greedy_batch(self._h, s.size, s.ctypes.data, t.ctypes.data, p.ctypes.data, int(steps), out.ctypes.data))
+        return out
+
+    def read_seq_cache(self, seq, name, layer=-1):
+        """Sequence `seq`'s key_cache / value_cache ([L][S][d] flat, or one layer's [S][d])."""
+        c = self.cfg
+        n = c.seq_len * c.dim * (c.n_layers if layer < 0 else 1)
+        out = np.empty(n, dtype=np.float32)
+        _check(lib().l2_read_seq_cache(self._h, int(seq), STATE_IDS[name], int(layer), out.ctypes.data, n))
+        return out
 
     def read_state(self, name, layer=-1):
         c = self.cfg
