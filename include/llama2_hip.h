@@ -26,7 +26,8 @@ extern "C" {
  * 4 (round 5): option key L2_OPT_AQL_QUEUE
  * 5 (round 6): option keys L2_OPT_PREFILL_F32_MFMA, L2_OPT_CHECK_POS; l2_dispatch_reason
  * The batched decode of independent sequences (l2_seq_reserve .. l2_read_seq_cache, option key L2_OPT_SEQS) joined the surface without a
- * version step: it only adds, and a binding detects it by the presence of the l2_seq_reserve symbol. */
+ * version step: it only adds, and a binding detects it by the presence of the l2_seq_reserve symbol.  So did its sampled loop
+ * (l2_decode_sample_batch, option keys L2_OPT_BATCH_SAMPLED_TOKENS / _SERIAL), detected by its own symbol. */
 #define L2_ABI_VERSION 5
 
 enum {
@@ -98,7 +99,9 @@ enum {
                                  neither restarts at 0 nor continues the sequence -- the reference's loop feeds pos = 0, 1, 2, ... (llama2.ts:464,
                                  496) and attention reads whatever rows 0 .. pos - 1 the cache holds; 0 (default): any position is accepted.
                                  Applies per sequence to the batch calls below (sequence 0 shares its position with l2_forward / l2_prefill) */
-  L2_OPT_SEQS = 11            /* read-only: sequences reserved by l2_seq_reserve (0 before it) */
+  L2_OPT_SEQS = 11,           /* read-only: sequences reserved by l2_seq_reserve (0 before it) */
+  L2_OPT_BATCH_SAMPLED_TOKENS = 12, /* read-only: tokens l2_decode_sample_batch has sampled (temperature != 0), saturating */
+  L2_OPT_BATCH_SAMPLED_SERIAL = 13  /* read-only: of those, the ones the margin form's serial loop picked */
 };
 
 typedef struct l2_ctx l2_ctx;
@@ -223,6 +226,18 @@ int l2_forward_batch(l2_ctx* ctx, int n, const int32_t* seqs, const int32_t* tok
  * (first maximum, llama2.ts:364-366).  tokens_out is n x steps, row-major per sequence.  Does not stop at BOS.  pos0[i] + steps <= seq_len. */
 int l2_decode_greedy_batch(l2_ctx* ctx, int n, const int32_t* seqs, const int32_t* first_tokens, const int32_t* pos0,
                            int steps, int32_t* tokens_out);
+/* The sampled device loop over n sequences: row i feeds first_tokens[i] at pos0[i] of sequence seqs[i], then its own pick, `steps` times,
+ * each row with its own settings (llama2.ts:476-493): temperature[i] == 0 takes the argmax (the rules of l2_decode_greedy_batch, no draw,
+ * rng_state[i] left alone); otherwise logits / temperature[i] (any sign), softmax, then `sample` when topp[i] <= 0 or >= 1, else
+ * `sample_topp`, with one xorshift* draw from rng_state[i] per token.  The tokens are exactly what the reference's sampler returns when
+ * it is fed this path's own logits (those of l2_forward_batch for the same rows).  tokens_out is n x steps, row-major per sequence;
+ * rng_state is written back only on success.  Does not stop at BOS.  Argument rules of l2_decode_greedy_batch, plus: L2_E_ARG for a null
+ * temperature / topp / rng_state or a NaN setting; L2_E_CONFIG when vocab_size exceeds the device sampler's limit and a row samples.
+ * Every phase of the device sampler runs once per step for all rows (the margin form of l2_decode_sample, row by row); its
+ * L2_SAMPLER_FORCE_SERIAL test hook applies, the A/B forms L2_SAMPLER_CHAIN / L2_SAMPLER_SERIAL do not.  The single-sequence sampler's
+ * state and L2_OPT_SAMPLED_TOKENS / _SERIAL are left alone. */
+int l2_decode_sample_batch(l2_ctx* ctx, int n, const int32_t* seqs, const int32_t* first_tokens, const int32_t* pos0, int steps,
+                           const double* temperature, const double* topp, uint64_t* rng_state, int32_t* tokens_out);
 /* Read sequence `seq`'s key / value cache (which = L2_S_KEY_CACHE / L2_S_VALUE_CACHE; layer -1 = all), like l2_read_state. */
 int l2_read_seq_cache(l2_ctx* ctx, int seq, int which, int layer, float* out, size_t n_floats);
 

@@ -7,6 +7,7 @@
 // lives in device tables -- row t feeds token tok[t] at position pos[t] of sequence seq[t] -- read by the q / k / v epilogue (RoPE
 // and the cache stores: pf_emit<MODE_QKV_ROWS>), the attention kernel (attention.hip.h: bt_attn_tile_kernel, one workgroup per
 // (head, row) over that row's own cache) and the per-row pick below, so one recorded step serves every placement of the sequences.
+// The sampled step (l2_decode_sample_batch) ends with the row form of the device sampler (sampler.h: BatchSampler) and bt_pick_kernel.
 // The step runs as a replayed hipGraph or eager launches on the context's stream, never on the library's AQL queue: every kernel
 // boundary carries the usual acquire / release, and the tables the pick advances are read with plain loads by the next step.
 #pragma once
@@ -17,35 +18,24 @@ namespace l2k {
 // Row r's pick (llama2.ts:364-366: first maximum, the argmax_key rules -- NaN at index 0, +-0, +-inf), then the step's bookkeeping:
 // the token is fed next (tok[r]), recorded at out[r * out_stride + pos[r] - start[r]], and the row moves to the next position.
 __global__ void __launch_bounds__(1024) bt_argmax_kernel(const float* logits, int V, int* tok, int* pos, const int* start, int* out, int out_stride) {
-  __shared__ unsigned long long sk[16];
-  const int r = blockIdx.x, tid = threadIdx.x;
-  const float* lg = logits + (size_t)r * V;
-  unsigned long long best = 0;
-  if ((V & 3) == 0) {   // rows start 16-byte aligned
-    const f4* l4 = reinterpret_cast<const f4*>(lg);
-    for (int c = tid; c < V / 4; c += 1024) {
-      const f4 v = l4[c];
-      unsigned long long k = argmax_key(v.x, 4 * c); best = k > best ? k : best;
-      k = argmax_key(v.y, 4 * c + 1); best = k > best ? k : best;
-      k = argmax_key(v.z, 4 * c + 2); best = k > best ? k : best;
-      k = argmax_key(v.w, 4 * c + 3); best = k > best ? k : best;
+#include "bt_argmax_body.inc"
+}
+
+// The sampled step's last launch: row r takes its argmax when its temperature params[2 r] is 0 (no draw), else the token the row
+// sampler left in pick[4 r] (sampler.h: BatchSampler); every row's pick is applied exactly once, as bt_argmax_kernel does it.
+__global__ void __launch_bounds__(1024) bt_pick_kernel(const float* logits, int V, const double* params, int* pick, int* tok, int* pos, const int* start,
+                                                       int* out, int out_stride) {
+  if (params[2 * blockIdx.x] != 0.0) {
+    if (threadIdx.x == 0) {
+      const int q = blockIdx.x, p = pos[q], bi = pick[4 * q];
+      pick[4 * q + 2] = 0;                                     // the row sampler's advance() writes its token at step 0 again
+      out[(size_t)q * out_stride + (p - start[q])] = bi;
+      tok[q] = bi;
+      pos[q] = p + 1;
     }
-  } else {
-    for (int i = tid; i < V; i += 1024) { const unsigned long long k = argmax_key(lg[i], i); best = k > best ? k : best; }
+    return;
   }
-  best = wave_max_u64(best);
-  if ((tid & 63) == 0) sk[tid >> 6] = best;
-  __syncthreads();
-  if (tid < 64) {
-    best = wave_max_u64(tid < 16 ? sk[tid] : 0ull);
-    if (tid == 0) {
-      const int bi = (best == 0) ? 0 : (int)~(unsigned)best;   // nothing but NaN: reduce() keeps index 0
-      const int p = pos[r];
-      out[(size_t)r * out_stride + (p - start[r])] = bi;
-      tok[r] = bi;
-      pos[r] = p + 1;
-    }
-  }
+#include "bt_argmax_body.inc"
 }
 
 }  // namespace l2k

@@ -1,5 +1,5 @@
-// batch_host.hip.h -- host side of batched greedy decode (batch.hip.h): l2_seq_reserve, l2_seq_prefill, l2_forward_batch,
-// l2_decode_greedy_batch, l2_read_seq_cache.
+// batch_host.hip.h -- host side of batched decode (batch.hip.h): l2_seq_reserve, l2_seq_prefill, l2_forward_batch,
+// l2_decode_greedy_batch, l2_decode_sample_batch, l2_read_seq_cache.
 // Part of the one translation unit llama2_hip.hip (included there, in order); not a stand-alone header.
 #pragma once
 
@@ -19,6 +19,9 @@ struct BatchState {
   int* out = nullptr;                     // device [BT_MAX][S]: tokens picked by row r at position p -> out[r][p - start[r]]
   float *x = nullptr, *xn = nullptr, *q = nullptr, *xb = nullptr, *hb = nullptr, *logits = nullptr;   // [BT_MAX][d | h | V]
   hipGraphExec_t g[BT_MAX + 1] = {};      // the recorded step per row count
+  hipGraphExec_t gs[BT_MAX + 1] = {};     // the recorded sampled step per row count (forward + row sampler + bt_pick_kernel)
+  l2s::BatchSampler* smp = nullptr;       // the row sampler's buffers: allocated at the first l2_decode_sample_batch
+  unsigned long long smp_stats[2] = {};   // {tokens sampled, of those by the serial loop} over every l2_decode_sample_batch
   std::vector<uintptr_t> sig;             // what the recorded steps baked in (weight addresses, options)
   int* seq_of() const { return tab; }
   int* tok_of() const { return tab + BT_MAX; }
@@ -28,6 +31,7 @@ struct BatchState {
 
 static void bt_drop_graphs(BatchState* b) {
   for (auto& g : b->g) if (g) { hipGraphExecDestroy(g); g = nullptr; }
+  for (auto& g : b->gs) if (g) { hipGraphExecDestroy(g); g = nullptr; }
 }
 
 static void batch_free(l2_ctx* c) {
@@ -38,6 +42,7 @@ static void batch_free(l2_ctx* c) {
   void* dev[] = {b->d_kc, b->d_vc, b->tab, b->out, b->x, b->xn, b->q, b->xb, b->hb, b->logits};
   for (void* p : dev) if (p) hipFree(p);
   if (b->h_tab) hipHostFree(b->h_tab);
+  if (b->smp) { l2s::destroy_rows(b->smp); delete b->smp; }
   delete b;
   c->bt = nullptr;
 }
@@ -152,8 +157,8 @@ static hipError_t launch_bt_attn(const l2_ctx* c, const AttnArgs& a, const AttnR
   return hipGetLastError();
 }
 
-// One batch step of n rows (tables already on the device): embed, the layers, final norm, classifier, per-row pick.
-static int bt_enqueue(l2_ctx* c, int n, hipStream_t st) {
+// The forward part of one batch step of n rows (tables already on the device): embed, the layers, final norm, classifier -> b->logits.
+static int bt_forward(l2_ctx* c, int n, hipStream_t st) {
   BatchState* b = c->bt;
   const int tt = (n > 32) ? 4 : (n > 16) ? 2 : 1, nt = 16 * tt;      // token rows the kernels see (whole 16-row MFMA tiles)
   const size_t d = c->d;
@@ -198,8 +203,28 @@ static int bt_enqueue(l2_ctx* c, int n, hipStream_t st) {
   bt_cls_weights(c, a);
   a.xin = b->xn; a.out = b->logits; a.n = c->d; a.rows = c->V; a.dim = c->d; a.nvalid = n;
   bt_gemm<MODE_CLS_ROWS>(c, a, tt, st);
-  // every row's pick (llama2.ts:364-366), fed next
+  LCHK(hipGetLastError());
+  return L2_OK;
+}
+
+// One greedy batch step: the forward part, then every row's argmax (llama2.ts:364-366), fed next.
+static int bt_enqueue(l2_ctx* c, int n, hipStream_t st) {
+  BatchState* b = c->bt;
+  int rc = bt_forward(c, n, st);
+  if (rc) return rc;
   hipLaunchKernelGGL(bt_argmax_kernel, dim3(n), dim3(1024), 0, st, (const float*)b->logits, c->V, b->tok_of(), b->pos_of(), (const int*)b->start_of(), b->out, c->S);
+  LCHK(hipGetLastError());
+  return L2_OK;
+}
+
+// One sampled batch step: the same forward part, the row sampler (every phase once for all n rows), then every row's pick applied.
+static int bt_enqueue_sampled(l2_ctx* c, int n, hipStream_t st) {
+  BatchState* b = c->bt;
+  int rc = bt_forward(c, n, st);
+  if (rc) return rc;
+  LCHK(l2s::enqueue_rows(*b->smp, b->logits, n, st));
+  hipLaunchKernelGGL(bt_pick_kernel, dim3(n), dim3(1024), 0, st, (const float*)b->logits, c->V, (const double*)b->smp->params, b->smp->pick,
+                     b->tok_of(), b->pos_of(), (const int*)b->start_of(), b->out, c->S);
   LCHK(hipGetLastError());
   return L2_OK;
 }
@@ -214,7 +239,8 @@ static std::vector<uintptr_t> bt_signature(const l2_ctx* c) {
 }
 
 // Upload the tables of n rows and run `steps` batch steps (recorded once per row count, replayed; eager with L2_OPT_USE_GRAPH = 0).
-static int bt_run(l2_ctx* c, int n, const int32_t* seqs, const int32_t* tokens, const int32_t* pos, int steps) {
+// `sampled`: the sampled step, whose per-row settings and rng states the caller has staged in b->smp's pinned tables.
+static int bt_run(l2_ctx* c, int n, const int32_t* seqs, const int32_t* tokens, const int32_t* pos, int steps, bool sampled = false) {
   BatchState* b = c->bt;
   int rc = ensure_ready(c);
   if (rc) return rc;
@@ -230,20 +256,28 @@ static int bt_run(l2_ctx* c, int n, const int32_t* seqs, const int32_t* tokens, 
     b->h_tab[3 * BT_MAX + i] = live ? pos[i] : 0;
   }
   HIPCHK(hipMemcpyAsync(b->tab, b->h_tab, 4 * BT_MAX * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  if (c->opt_graph && !b->g[n]) {
+  if (sampled) {
+    const l2s::BatchSampler& sm = *b->smp;
+    HIPCHK(l2s::reset_rows(sm, n, c->stream));      // "zero between tokens" holds whatever an earlier (aborted) call left
+    HIPCHK(hipMemcpyAsync(sm.params, sm.h_params, 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(sm.rng, sm.h_rng, (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+  }
+  hipGraphExec_t* rec = sampled ? b->gs : b->g;
+  auto enqueue = sampled ? bt_enqueue_sampled : bt_enqueue;
+  if (c->opt_graph && !rec[n]) {
     hipGraph_t graph = nullptr;
     LCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    rc = bt_enqueue(c, n, c->stream);
+    rc = enqueue(c, n, c->stream);
     const hipError_t e = hipStreamEndCapture(c->stream, &graph);
     if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
     if (e != hipSuccess) return fail(L2_E_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-    const hipError_t e2 = hipGraphInstantiate(&b->g[n], graph, nullptr, nullptr, 0);
+    const hipError_t e2 = hipGraphInstantiate(&rec[n], graph, nullptr, nullptr, 0);
     hipGraphDestroy(graph);
-    if (e2 != hipSuccess) { b->g[n] = nullptr; return fail(L2_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e2)); }
+    if (e2 != hipSuccess) { rec[n] = nullptr; return fail(L2_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e2)); }
   }
   for (int s = 0; s < steps; ++s) {
-    if (c->opt_graph) HIPCHK(hipGraphLaunch(b->g[n], c->stream));
-    else { rc = bt_enqueue(c, n, c->stream); if (rc) return rc; }
+    if (c->opt_graph) HIPCHK(hipGraphLaunch(rec[n], c->stream));
+    else { rc = enqueue(c, n, c->stream); if (rc) return rc; }
   }
   HIPCHK(hipStreamSynchronize(c->stream));
   for (int i = 0; i < n; ++i) bt_set_next(c, seqs[i], pos[i] + steps);
@@ -268,6 +302,48 @@ extern "C" int l2_decode_greedy_batch(l2_ctx* c, int n, const int32_t* seqs, con
   rc = bt_run(c, n, seqs, first_tokens, pos0, steps);
   if (rc) return rc;
   HIPCHK(hipMemcpy2D(tokens_out, (size_t)steps * sizeof(int32_t), c->bt->out, (size_t)c->S * sizeof(int), (size_t)steps * sizeof(int32_t), n, hipMemcpyDeviceToHost));
+  return L2_OK;
+}
+
+extern "C" int l2_decode_sample_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_t* first_tokens, const int32_t* pos0, int steps,
+                                      const double* temperature, const double* topp, uint64_t* rng_state, int32_t* tokens_out) {
+  int rc = bt_check(c, n, seqs, first_tokens, pos0, steps);
+  if (rc) return rc;
+  if (!temperature || !topp || !rng_state) return fail(L2_E_ARG, "null temperature / topp / rng_state");
+  if (!tokens_out && steps > 0) return fail(L2_E_ARG, "null tokens_out");
+  bool any = false;
+  for (int i = 0; i < n; ++i) {
+    if (!(temperature[i] == temperature[i]) || !(topp[i] == topp[i])) return fail(L2_E_ARG, "row %d: temperature / topp is NaN", i);
+    if (temperature[i] != 0.0) any = true;
+  }
+  if (any && c->V > l2s::MAX_VOCAB) return fail(L2_E_CONFIG, "device sampler supports vocabularies up to %d", (int)l2s::MAX_VOCAB);
+  if (steps == 0) return L2_OK;
+  BatchState* b = c->bt;
+  if (c->V > l2s::MAX_VOCAB) {      // every row greedy (no draw, rng states untouched) on a vocabulary the row sampler cannot hold
+    rc = bt_run(c, n, seqs, first_tokens, pos0, steps);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy2D(tokens_out, (size_t)steps * sizeof(int32_t), b->out, (size_t)c->S * sizeof(int), (size_t)steps * sizeof(int32_t), n, hipMemcpyDeviceToHost));
+    return L2_OK;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  if (!b->smp) {
+    l2s::BatchSampler* sm = new l2s::BatchSampler();
+    const hipError_t e = l2s::create_rows(sm, c->V, b->n_seqs);
+    if (e != hipSuccess) { delete sm; (void)hipGetLastError(); return fail(L2_E_HIP, "l2_decode_sample_batch: device memory for the row sampler: %s", hipGetErrorString(e)); }
+    b->smp = sm;
+  }
+  l2s::BatchSampler& sm = *b->smp;
+  HIPCHK(hipStreamSynchronize(c->stream));      // (the pinned tables: the previous call's copies have completed)
+  for (int i = 0; i < n; ++i) { sm.h_params[2 * i] = temperature[i]; sm.h_params[2 * i + 1] = topp[i]; sm.h_rng[i] = rng_state[i]; }
+  rc = bt_run(c, n, seqs, first_tokens, pos0, steps, true);
+  if (rc) return rc;
+  HIPCHK(hipMemcpy2D(tokens_out, (size_t)steps * sizeof(int32_t), b->out, (size_t)c->S * sizeof(int), (size_t)steps * sizeof(int32_t), n, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(sm.h_rng, sm.rng, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(sm.h_stats, sm.stats, 2 * (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; ++i) {
+    rng_state[i] = sm.h_rng[i];
+    for (int k = 0; k < 2; ++k) { const unsigned long long v = b->smp_stats[k] + sm.h_stats[2 * i + k]; b->smp_stats[k] = v < b->smp_stats[k] ? ~0ull : v; }
+  }
   return L2_OK;
 }
 

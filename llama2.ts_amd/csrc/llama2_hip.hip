@@ -1153,6 +1153,7 @@ extern "C" int l2_set_option(l2_ctx* c, int key, int value) {
     case L2_OPT_PREFILL_F32_MFMA: c->opt_pf_f32 = !!value; return L2_OK;
     case L2_OPT_CHECK_POS: c->opt_pos_check = !!value; return L2_OK;
     case L2_OPT_PACKED_MIB: case L2_OPT_WEIGHT_MIB: case L2_OPT_SAMPLED_TOKENS: case L2_OPT_SAMPLED_SERIAL: case L2_OPT_SEQS:
+    case L2_OPT_BATCH_SAMPLED_TOKENS: case L2_OPT_BATCH_SAMPLED_SERIAL:
       return fail(L2_E_ARG, "option %d is read-only", key);
     default: return fail(L2_E_ARG, "unknown option %d", key);
   }
@@ -1168,6 +1169,11 @@ extern "C" int l2_get_option(l2_ctx* c, int key, int* value) {
     case L2_OPT_PREFILL_F32_MFMA: *value = c->opt_pf_f32; return L2_OK;
     case L2_OPT_CHECK_POS: *value = c->opt_pos_check; return L2_OK;
     case L2_OPT_SEQS: *value = c->bt ? c->bt->n_seqs : 0; return L2_OK;
+    case L2_OPT_BATCH_SAMPLED_TOKENS: case L2_OPT_BATCH_SAMPLED_SERIAL: {
+      const unsigned long long v = c->bt ? c->bt->smp_stats[key == L2_OPT_BATCH_SAMPLED_SERIAL ? 1 : 0] : 0;
+      *value = v > 0x7fffffffull ? 0x7fffffff : (int)v;
+      return L2_OK;
+    }
     case L2_OPT_PACKED_MIB: {
       size_t floats = 0;
       if (c->packed_valid) for (int m = 0; m < 5; ++m) if (c->packed[m].buf) floats += c->packed[m].layer_elems * (size_t)(m == MODE_CLS ? 1 : c->L);

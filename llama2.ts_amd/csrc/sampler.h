@@ -67,6 +67,54 @@ hipError_t enqueue(const Sampler& s, const float* logits, bool topp_mode, int* t
 // {tokens the margin form picked, of those by its serial loop} since create(); synchronous.
 hipError_t read_stats(const Sampler& s, unsigned long long out[2], hipStream_t st);
 
+// Row form for the batched decode (batch_host.hip.h): every phase of the margin form launched ONCE per step for n rows, the row on a spare
+// grid dimension, every per-row buffer at a row stride.  Row r reads logits + r V and its settings params[2 r] = {temperature, topp},
+// draws from rng[r], leaves its token in pick[4 r] (bt_pick_kernel in batch.hip.h applies it) and counts into stats[2 r ..].  A row whose
+// mode a phase does not serve (temperature 0: argmax in bt_pick_kernel; plain sample; sample_topp) leaves that phase at entry, so one
+// recording serves any mix of settings.  The classifier folds no argmax keys here: every sampled row takes the max pass.
+// L2_SAMPLER_FORCE_SERIAL (behind L2_TEST_HOOKS) is honoured: it is the margin form's own branch.  The A/B forms L2_SAMPLER_CHAIN and
+// L2_SAMPLER_SERIAL are NOT carried into the row form.
+struct BatchSampler {
+  int V = 0, G = 0, rows = 0;
+  size_t P = 0;                  // row stride of the per-element buffers (V padded to whole sort tiles)
+  size_t R = 0;                  // row stride of the run records (G * 1025)
+  float* probs = nullptr;        // (rows x P) exps of the scaled logits
+  float* run_p = nullptr;        // (rows x P) sorted tiles (top-p)
+  int* idx = nullptr;            // (rows x P) their ids
+  float* sorted = nullptr;       // (rows x P) probabilities in descending order
+  int* ids = nullptr;            // (rows x P) ids beside them
+  unsigned* rank_acc = nullptr;  // (rows x P) rank merge accumulators, zero between tokens
+  double* part = nullptr;        // (rows x G) tile sums of the exps
+  double* part2 = nullptr;       // (rows x G) tile sums of the probabilities
+  double* amb = nullptr;         // (rows x G)
+  double* part_sorted = nullptr; // (rows x G) zero between tokens
+  void* recs = nullptr;          // (rows x R) xs::Run records of the exps (top-p)
+  int* cnt = nullptr;            // (rows x G)
+  double* runS = nullptr;        // (rows x R) per run state when the runs do not fit in LDS
+  int* runEnd = nullptr;
+  int* runBad = nullptr;
+  double* total = nullptr;       // (rows) exact total of the exps (top-p)
+  unsigned* mxkey = nullptr;     // (rows) zero between tokens
+  unsigned* ticket = nullptr;    // (rows) zero between tokens
+  double* params = nullptr;      // (rows x 2) {temperature, topp}
+  unsigned long long* rng = nullptr;     // (rows) xorshift* states
+  unsigned long long* stats = nullptr;   // (rows x 2) {tokens sampled, of those by the serial loop}
+  int* pick = nullptr;           // (rows x 4) the sampled rows' picks: advance()'s record {token, count, step, token}; bt_pick_kernel reads
+                                 // the token and puts step back to 0
+  double* h_params = nullptr;    // pinned staging of params / rng / stats
+  unsigned long long* h_rng = nullptr;
+  unsigned long long* h_stats = nullptr;
+  bool force_serial = false;
+};
+// Buffers for `rows` rows of a V-entry vocabulary (V <= MAX_VOCAB); on failure nothing is held.
+hipError_t create_rows(BatchSampler* s, int V, int rows);
+void destroy_rows(BatchSampler* s);
+// The scratch that must be zero between tokens (a call that ended early may have left it otherwise) and the per-row counters.
+hipError_t reset_rows(const BatchSampler& s, int n, hipStream_t st);
+// The sampler phases of one batch step for rows 0 .. n-1 (logits: n rows of V floats).  Plain HIP launches (recordable by stream
+// capture), never the AQL recorder.
+hipError_t enqueue_rows(const BatchSampler& s, const float* logits, int n, hipStream_t st);
+
 // Diagnostic: running sums S_i = fl(S_{i-1} + x_i) of n <= MAX_VOCAB non-negative fp32 values, by the exact parallel
 // algorithm (synchronous).
 hipError_t running_sums(const float* x_dev, int n, double* prefix_dev, hipStream_t st);

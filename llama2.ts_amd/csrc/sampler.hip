@@ -86,10 +86,94 @@ __device__ __forceinline__ void advance(int* tokpos, int* tokens_out, int next) 
   tokpos[0] = next; tokpos[1] = tokpos[1] + 1; tokpos[2] = step + 1;
 }
 
+// Which picker a batch row runs (llama2.ts:477-487): 0 argmax (temperature 0), 1 sample, 2 sample_topp (0 < topp < 1).
+__device__ __forceinline__ int row_mode(const double* params) {
+  const double t = params[0], p = params[1];
+  return t == 0.0 ? 0 : (p <= 0.0 || p >= 1.0) ? 1 : 2;
+}
+
 #include "sampler_serial.hip.h"
 #include "sampler_chain.hip.h"
 #include "sampler_sort.hip.h"
 #include "sampler_margin.hip.h"
+
+// ---- row forms of the margin form's phases (BatchSampler): row r = blockIdx.y (the rank merge: blockIdx.z) ----------------------
+__global__ void __launch_bounds__(TN) scaled_max_rows_kernel(const float* logits, int V, const double* params, unsigned* mxkey) {
+  const int r = blockIdx.y;
+  if (row_mode(params + 2 * r) == 0) return;
+  scaled_max_body(logits + (size_t)r * V, V, params + 2 * r, mxkey + r);
+}
+
+__global__ void __launch_bounds__(TN) exp_rows_kernel(const float* logits, int V, const double* params, const unsigned* mxkey, float* probs, double* part,
+                                                       size_t P, int G) {
+  __shared__ double wsum[NWV];
+  const int r = blockIdx.y;
+  if (row_mode(params + 2 * r) == 0) return;
+  exp_body(logits + (size_t)r * V, V, params + 2 * r, mxkey + r, nullptr, probs + r * P, part + (size_t)r * G, wsum);
+}
+
+// Row r's view of the margin arguments (a: row 0's pointers).  The pick goes through advance() into the row's record pick[4 r ..]
+// {token, count, step, token} whose step bt_pick_kernel puts back to 0.
+__device__ __forceinline__ MarginArgs margin_row(const MarginArgs& a, int r, size_t P) {
+  MarginArgs m = a;
+  const size_t g = (size_t)r * a.G;
+  m.exps = a.exps + r * P; m.part = a.part + g; m.part2 = a.part2 + g; m.amb = a.amb + g; m.ticket = a.ticket + r;
+  m.sorted = a.sorted + r * P; m.ids = a.ids + r * P; m.part_sorted = a.part_sorted + g; m.params = a.params + 2 * r; m.rng = a.rng + r;
+  m.tokpos = a.tokpos + 4 * r; m.tokens_out = a.tokpos + 4 * r + 3; m.mxkey = a.mxkey + r; m.amax = nullptr; m.stats = a.stats + 2 * r;
+  return m;
+}
+
+__global__ void __launch_bounds__(TN) sample_margin_rows_kernel(const MarginArgs rows, size_t P) {
+  if (row_mode(rows.params + 2 * blockIdx.y) != 1) return;
+  const MarginArgs a = margin_row(rows, blockIdx.y, P);
+  __shared__ MarginShared sh;
+#include "sample_margin_body.inc"
+}
+
+__global__ void __launch_bounds__(TN) topp_margin_rows_kernel(const MarginArgs rows, size_t P) {
+  if (row_mode(rows.params + 2 * blockIdx.y) != 2) return;
+  const MarginArgs a = margin_row(rows, blockIdx.y, P);
+  __shared__ MarginShared sh;
+#include "topp_margin_body.inc"
+}
+
+__global__ void __launch_bounds__(TN) runs_total_rows_kernel(ChainArgs rows, size_t P, size_t R, const double* params, Run* recs0, int* cnt0, unsigned* ticket0,
+                                                              double* total0) {
+  const int r = blockIdx.y;
+  if (row_mode(params + 2 * r) != 2) return;
+  const size_t g = (size_t)r * rows.G;
+  ChainArgs a = rows;
+  a.x += r * P; a.part += g; a.recs += r * R; a.cnt += g; a.S += r * R; a.End += r * R; a.Bad += r * R;
+  Run* const recs = recs0 + r * R;
+  int* const cnt = cnt0 + g;
+  unsigned* const ticket = ticket0 + r;
+  double* const total = total0 + r;
+  __shared__ ChainShared sh;
+#include "runs_total_body.inc"
+}
+
+__global__ void __launch_bounds__(WT) sort_tile_wide_rows_kernel(const float* exps, const double* total, int V, float* run_p, int* run_id, size_t P,
+                                                                  const double* params) {
+  __shared__ u64 xch[STILE];
+  const int r = blockIdx.y;
+  if (row_mode(params + 2 * r) != 2) return;
+  sort_tile_wide_body(exps + r * P, total + r, V, run_p + r * P, run_id + r * P, xch);
+}
+
+__global__ void __launch_bounds__(RT) sort_rank_rows_kernel(const float* run_p0, const int* run_id0, int GS, int G, unsigned* acc0, float* sorted0, int* ids0,
+                                                             double* part0, size_t P, const double* params) {
+  const size_t r = blockIdx.z;
+  if (row_mode(params + 2 * r) != 2) return;
+  const float* const run_p = run_p0 + r * P;
+  const int* const run_id = run_id0 + r * P;
+  unsigned* const acc = acc0 + r * P;
+  float* const sorted = sorted0 + r * P;
+  int* const ids = ids0 + r * P;
+  double* const part = part0 + r * G;
+  __shared__ int lds_p[RANK_TQ * STILE];
+  __shared__ double lpart[MAX_VOCAB / TILE];
+#include "sort_rank_body.inc"
+}
 
 // Stage 1 = the exps (recs / cnt), stage 2 = the probabilities, in index or in sorted order (recs2 / cnt2, cq / cm): two
 // sets of run records because the fused kernels write stage 2 while other workgroups still read stage 1.
@@ -254,6 +338,91 @@ hipError_t enqueue(const Sampler& s, const float* logits, bool topp_mode, int* t
   pick.tokpos = tokpos; pick.tokens_out = tokens_out; pick.amax = amax;
   pick.ids = topp_mode ? s.idx_sorted : nullptr;
   return launch_chain(pick, topp_mode ? CHAIN_TOPP : CHAIN_SAMPLE, st);
+}
+
+hipError_t create_rows(BatchSampler* s, int V, int rows) {
+  if (V <= 0 || V > MAX_VOCAB || rows <= 0) return hipErrorInvalidValue;
+  s->V = V; s->rows = rows;
+  s->G = (V + TILE - 1) / TILE;
+  s->P = (size_t)((V + STILE - 1) / STILE) * STILE;
+  s->R = (size_t)s->G * (TILE + 1);
+  const size_t n = (size_t)rows, P = s->P, R = s->R, G = (size_t)s->G;
+  hipError_t e;
+#define L2S(x) do { e = (x); if (e != hipSuccess) { destroy_rows(s); return e; } } while (0)
+  L2S(hipMalloc(&s->probs, n * P * 4));
+  L2S(hipMalloc(&s->run_p, n * P * 4));
+  L2S(hipMalloc(&s->idx, n * P * 4));
+  L2S(hipMalloc(&s->sorted, n * P * 4));
+  L2S(hipMalloc(&s->ids, n * P * 4));
+  L2S(hipMalloc(&s->rank_acc, n * P * sizeof(unsigned)));
+  L2S(hipMalloc(&s->part, n * G * sizeof(double)));
+  L2S(hipMalloc(&s->part2, n * G * sizeof(double)));
+  L2S(hipMalloc(&s->amb, n * G * sizeof(double)));
+  L2S(hipMalloc(&s->part_sorted, n * G * sizeof(double)));
+  L2S(hipMalloc(&s->recs, n * R * sizeof(Run)));
+  L2S(hipMalloc(&s->cnt, n * G * sizeof(int)));
+  L2S(hipMalloc(&s->runS, n * R * sizeof(double)));
+  L2S(hipMalloc(&s->runEnd, n * R * sizeof(int)));
+  L2S(hipMalloc(&s->runBad, n * R * sizeof(int)));
+  L2S(hipMalloc(&s->total, n * sizeof(double)));
+  L2S(hipMalloc(&s->mxkey, n * sizeof(unsigned)));
+  L2S(hipMalloc(&s->ticket, n * sizeof(unsigned)));
+  L2S(hipMalloc(&s->params, 2 * n * sizeof(double)));
+  L2S(hipMalloc(&s->rng, n * sizeof(unsigned long long)));
+  L2S(hipMalloc(&s->stats, 2 * n * sizeof(unsigned long long)));
+  L2S(hipMalloc(&s->pick, 4 * n * sizeof(int)));
+  L2S(hipHostMalloc((void**)&s->h_params, 2 * n * sizeof(double), 0));
+  L2S(hipHostMalloc((void**)&s->h_rng, n * sizeof(unsigned long long), 0));
+  L2S(hipHostMalloc((void**)&s->h_stats, 2 * n * sizeof(unsigned long long), 0));
+#undef L2S
+  const char* g_ = getenv("L2_TEST_HOOKS");
+  const char* f_ = getenv("L2_SAMPLER_FORCE_SERIAL");
+  s->force_serial = g_ && atoi(g_) != 0 && f_ && atoi(f_) != 0;
+  return hipSuccess;
+}
+
+void destroy_rows(BatchSampler* s) {
+  void* bufs[] = {s->probs, s->run_p, s->idx, s->sorted, s->ids, s->rank_acc, s->part, s->part2, s->amb, s->part_sorted, s->recs, s->cnt,
+                  s->runS, s->runEnd, s->runBad, s->total, s->mxkey, s->ticket, s->params, s->rng, s->stats, s->pick};
+  for (void* b : bufs) if (b) (void)hipFree(b);
+  void* host[] = {s->h_params, s->h_rng, s->h_stats};
+  for (void* b : host) if (b) (void)hipHostFree(b);
+  *s = BatchSampler();
+}
+
+hipError_t reset_rows(const BatchSampler& s, int n, hipStream_t st) {
+  hipError_t e;
+  if ((e = hipMemsetAsync(s.rank_acc, 0, (size_t)n * s.P * sizeof(unsigned), st)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(s.part_sorted, 0, (size_t)n * s.G * sizeof(double), st)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(s.mxkey, 0, (size_t)n * sizeof(unsigned), st)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(s.ticket, 0, (size_t)n * sizeof(unsigned), st)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(s.pick, 0, (size_t)4 * n * sizeof(int), st)) != hipSuccess) return e;
+  return hipMemsetAsync(s.stats, 0, (size_t)2 * n * sizeof(unsigned long long), st);
+}
+
+// The phases of sampler.hip's enqueue() (margin form, no argmax keys), each launched once for all n rows: max, exps; plain sample's pick;
+// top-p's exact total + runs, tile sort, rank merge, pick.
+hipError_t enqueue_rows(const BatchSampler& s, const float* logits, int n, hipStream_t st) {
+  if (n < 1 || n > s.rows) return hipErrorInvalidValue;
+  const int gs = (s.V + STILE - 1) / STILE;
+  hipLaunchKernelGGL(scaled_max_rows_kernel, dim3(s.G, n), dim3(TN), 0, st, logits, s.V, (const double*)s.params, s.mxkey);
+  hipLaunchKernelGGL(exp_rows_kernel, dim3(s.G, n), dim3(TN), 0, st, logits, s.V, (const double*)s.params, (const unsigned*)s.mxkey, s.probs, s.part, s.P, s.G);
+  MarginArgs m = {};
+  m.exps = s.probs; m.part = s.part; m.V = s.V; m.G = s.G; m.part2 = s.part2; m.amb = s.amb; m.ticket = s.ticket;
+  m.sorted = s.sorted; m.ids = s.ids; m.part_sorted = s.part_sorted; m.params = s.params; m.rng = s.rng;
+  m.tokpos = s.pick; m.tokens_out = nullptr; m.mxkey = s.mxkey; m.amax = nullptr; m.stats = s.stats; m.force_serial = s.force_serial ? 1 : 0;
+  hipLaunchKernelGGL(sample_margin_rows_kernel, dim3(s.G, n), dim3(TN), 0, st, m, s.P);
+  ChainArgs c = {};
+  c.x = s.probs; c.V = s.V; c.G = s.G; c.part = s.part; c.recs = (const Run*)s.recs; c.cnt = s.cnt;
+  c.S = s.runS; c.End = s.runEnd; c.Bad = s.runBad; c.params = s.params; c.rng = s.rng; c.mxkey = s.mxkey;
+  hipLaunchKernelGGL(runs_total_rows_kernel, dim3(s.G, n), dim3(TN), 0, st, c, s.P, s.R, (const double*)s.params, (Run*)s.recs, s.cnt, s.ticket, s.total);
+  hipLaunchKernelGGL(sort_tile_wide_rows_kernel, dim3(gs, n), dim3(WT), 0, st, (const float*)s.probs, (const double*)s.total, s.V, s.run_p, s.idx, s.P,
+                     (const double*)s.params);
+  const int ne = gs * STILE;
+  hipLaunchKernelGGL(sort_rank_rows_kernel, dim3((ne + RT - 1) / RT, (gs + RANK_TQ - 1) / RANK_TQ, n), dim3(RT), 0, st, (const float*)s.run_p,
+                     (const int*)s.idx, gs, s.G, s.rank_acc, s.sorted, s.ids, s.part_sorted, s.P, (const double*)s.params);
+  hipLaunchKernelGGL(topp_margin_rows_kernel, dim3(1, n), dim3(TN), 0, st, m, s.P);
+  return hipGetLastError();
 }
 
 }  // namespace l2s

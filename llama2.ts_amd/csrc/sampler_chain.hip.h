@@ -162,7 +162,7 @@ __device__ __forceinline__ unsigned order_key(float x) { const unsigned b = __fl
 __device__ __forceinline__ float order_value(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 // max over state.logits[q] / temperature (:482, softmax :183-186)
-__global__ void __launch_bounds__(TN) scaled_max_kernel(const float* logits, int V, const double* params, unsigned* mxkey) {
+__device__ __forceinline__ void scaled_max_body(const float* logits, int V, const double* params, unsigned* mxkey) {
   float v[IT];
   load_tile(logits, V, blockIdx.x, v);
   const double T = params[0];
@@ -174,13 +174,15 @@ __global__ void __launch_bounds__(TN) scaled_max_kernel(const float* logits, int
   for (int off = 32; off > 0; off >>= 1) key = max(key, (unsigned)__shfl_xor((int)key, off, 64));
   if ((threadIdx.x & 63) == 0) atomicMax(mxkey, key);
 }
+__global__ void __launch_bounds__(TN) scaled_max_kernel(const float* logits, int V, const double* params, unsigned* mxkey) {
+  scaled_max_body(logits, V, params, mxkey);
+}
 
 // probs[i] = (float)exp(x_i - max)  (:187) and the tile sums for the approximate prefix
 // (amax != null, temperature > 0: the classifier already folded max(logits) into its argmax keys -- kernels.hip.h
 // argmax_key -- and x -> (float)(x / T) is monotone, so the maximum of the scaled logits is the scaled maximum)
-__global__ void __launch_bounds__(TN) exp_kernel(const float* logits, int V, const double* params, const unsigned* mxkey, const unsigned long long* amax,
-                                                  float* probs, double* part) {
-  __shared__ double wsum[NWV];
+__device__ __forceinline__ void exp_body(const float* logits, int V, const double* params, const unsigned* mxkey, const unsigned long long* amax,
+                                         float* probs, double* part, double* wsum) {
   float v[IT];
   load_tile(logits, V, blockIdx.x, v);
   const double T = params[0];
@@ -202,6 +204,11 @@ __global__ void __launch_bounds__(TN) exp_kernel(const float* logits, int V, con
   }
   const double t = tile_total(v, wsum);
   if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+__global__ void __launch_bounds__(TN) exp_kernel(const float* logits, int V, const double* params, const unsigned* mxkey, const unsigned long long* amax,
+                                                  float* probs, double* part) {
+  __shared__ double wsum[NWV];
+  exp_body(logits, V, params, mxkey, amax, probs, part, wsum);
 }
 
 __global__ void __launch_bounds__(TN) tile_sums_kernel(const float* x, int V, double* part) {
@@ -532,20 +539,7 @@ __global__ void __launch_bounds__(TN) chain_kernel(ChainArgs a) {
 // write-through stores, every wave drains them, one lane takes a ticket; the workgroup that gets the last one walks the chain.
 __global__ void __launch_bounds__(TN) runs_total_kernel(ChainArgs a, Run* recs, int* cnt, unsigned* ticket, double* total) {
   __shared__ ChainShared sh;
-  float v[IT];
-  load_tile(a.x, a.V, blockIdx.x, v);
-  Elems el;
-  tile_scan(v, tile_base(a.part, blockIdx.x), sh.tile, el);
-  emit_runs<false, true>(el, v, a.V, blockIdx.x, recs, cnt, nullptr, nullptr);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) sh.slot = (int)__hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  if (sh.slot != a.G - 1) return;
-  __syncthreads();
-  bool in_lds;
-  chain_total<true>(a, sh, &in_lds);
-  if (threadIdx.x == 0) { *total = sh.val; __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+#include "runs_total_body.inc"
 }
 
 // The exact softmax denominator, recomputed by every workgroup of the kernel that needs it next (a walk over ~50 runs is

@@ -27,6 +27,7 @@ STATE_IDS = dict(x=S_X, xb=S_XB, xb2=S_XB2, hb=S_HB, hb2=S_HB2, q=S_Q, k=S_K, v=
                  key_cache=S_KEY_CACHE, value_cache=S_VALUE_CACHE)
 OPT_EXACT_ATTENTION, OPT_USE_GRAPH, OPT_KEEP_STATE, OPT_PACKED_MIB, OPT_WEIGHT_MIB, OPT_SAMPLED_TOKENS, OPT_SAMPLED_SERIAL, OPT_AQL_QUEUE, OPT_PREFILL_F32_MFMA, OPT_CHECK_POS = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 OPT_SEQS = 11      # read-only: sequences reserved by seq_reserve (0 before it)
+OPT_BATCH_SAMPLED_TOKENS, OPT_BATCH_SAMPLED_SERIAL = 12, 13   # read-only: decode_sample_batch's sampled tokens, of those by the serial loop
 F_GQA, F_GENERATE_ROPE = 1, 2     # l2_create_ex flags
 TP_SOLO_ID = b"L2-SOLO-SHARD-TIMING"   # l2_create_tp id of a shard-timing context (include/llama2_hip.h: L2_TP_SOLO_ID)
 
@@ -35,7 +36,8 @@ ABI_SYMBOLS = ["l2_abi_version", "l2_device_count", "l2_last_error", "l2_create"
                "l2_create_tp", "l2_upload", "l2_synth_fill", "l2_read_tensor", "l2_forward", "l2_logits_host",
                "l2_decode_greedy", "l2_decode_sample", "l2_debug_running_sums", "l2_read_state", "l2_set_option", "l2_get_option", "l2_timer_start",
                "l2_timer_stop", "l2_bench_gemv", "l2_bench_decode", "l2_load_checkpoint", "l2_get_header", "l2_prefill", "l2_bench_dominant_in_situ", "l2_tp_mode", "l2_create_ex", "l2_bench_tokens", "l2_dispatch_reason",
-               "l2_seq_reserve", "l2_seq_prefill", "l2_forward_batch", "l2_decode_greedy_batch", "l2_read_seq_cache"]
+               "l2_seq_reserve", "l2_seq_prefill", "l2_forward_batch", "l2_decode_greedy_batch", "l2_read_seq_cache",
+               "l2_decode_sample_batch"]
 
 
 class L2Error(RuntimeError):
@@ -95,6 +97,7 @@ def lib():
     L.l2_forward_batch.argtypes = [vp, i32, vp, vp, vp, vp]
     L.l2_decode_greedy_batch.argtypes = [vp, i32, vp, vp, vp, i32, vp]
     L.l2_read_seq_cache.argtypes = [vp, i32, i32, i32, vp, sz]
+    L.l2_decode_sample_batch.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]
     for name in ABI_SYMBOLS:   # fail at load time, not at first use, if the .so is stale
         getattr(L, name)
     _lib = L
@@ -267,6 +270,21 @@ class Context:
         out = np.zeros((s.size, int(steps)), dtype=np.int32)
         _check(lib().l2_decode_greedy_batch(self._h, s.size, s.ctypes.data, t.ctypes.data, p.ctypes.data, int(steps), out.ctypes.data))
         return out
+
+    def decode_sample_batch(self, seqs, first_tokens, pos0, steps, temperature, topp, rng):
+        """Device-resident sampled loop over the rows (llama2.ts:476-493 per row).  temperature / topp: a scalar or one per row; rng: one
+        state per row (uint64).  Returns ((n, steps) tokens, [rng state after, per row])."""
+        s, t, p = self._rows(seqs, first_tokens, pos0)
+        n = s.size
+        temp = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, dtype=np.float64), (n,)))
+        tp = np.ascontiguousarray(np.broadcast_to(np.asarray(topp, dtype=np.float64), (n,)))
+        st = np.array([int(v) for v in rng], dtype=np.uint64)
+        if st.size != n:
+            raise ValueError("one rng state per row")
+        out = np.zeros((n, int(steps)), dtype=np.int32)
+        _check(lib().l2_decode_sample_batch(self._h, n, s.ctypes.data, t.ctypes.data, p.ctypes.data, int(steps), temp.ctypes.data,
+                                            tp.ctypes.data, st.ctypes.data, out.ctypes.data))
+        return out, [int(v) for v in st]
 
     def read_seq_cache(self, seq, name, layer=-1):
         """Sequence `seq`'s key_cache / value_cache ([L][S][d] flat, or one layer's [S][d])."""

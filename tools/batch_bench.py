@@ -8,6 +8,11 @@ tok/s, weight bytes per step / step time as a fraction of 8 TB/s, GEMM flops / s
 peak, and the ratio to the batch-1 device loop (l2_bench_decode) measured in the same process.
 
     python tools/batch_bench.py --model llama2_7b [--steps 64] [--out file.json]
+
+With --temperature T (and --topp P) every B is also timed through the sampled loop (l2_decode_sample_batch: the same setting on every
+row, seed 1000 + s for sequence s), in the same process.  The sampled run's first 8 steps are checked by replaying them through
+l2_forward_batch on the same context (same rows, same order) and the C oracle's sampler (tests/oracle_lib.py); exit status 1 on a
+mismatch.  Without the flags the tool times the greedy loop only, as before.
 """
 import argparse
 import json
@@ -29,8 +34,14 @@ def main():
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--batches", default="1,2,4,8,16,32,64", help="row counts to time (comma list)")
     ap.add_argument("--eager", action="store_true", help="eager launches instead of the replayed hipGraph (L2_OPT_USE_GRAPH = 0)")
+    ap.add_argument("--temperature", type=float, default=None, help="also time the sampled loop at this temperature (every row)")
+    ap.add_argument("--topp", type=float, default=1.0, help="top-p of the sampled loop (0 < p < 1: sample_topp)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    O = None
+    if args.temperature is not None:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import oracle_lib as O  # noqa: E402
     meta = json.load(open(os.path.join(ROOT, "tests", "golden", args.model + ".json")))
     hdr = configs.header(args.model)
     d, h, L, _H, _kv, V, _S = hdr
@@ -75,11 +86,31 @@ def main():
         good = all(toks[s].tolist() == picks[offsets[s]:offsets[s] + steps] for s in seqs)
         ok = ok and good
         step_s = dt / steps
-        rows.append({"B": B, "step_ms": round(step_s * 1e3, 3), "agg_tok_s": round(B / step_s, 1), "per_seq_tok_s": round(1 / step_s, 1),
-                     "hbm_frac": round(mat * 4 / step_s / HBM_BPS, 4), "fp64_mfma_frac": round(2.0 * B * mat / step_s / FP64_MFMA_FLOPS, 4),
-                     "x_batch1": round(B / step_s / b1, 2), "tokens_match": good})
+        row = {"B": B, "step_ms": round(step_s * 1e3, 3), "agg_tok_s": round(B / step_s, 1), "per_seq_tok_s": round(1 / step_s, 1),
+               "hbm_frac": round(mat * 4 / step_s / HBM_BPS, 4), "fp64_mfma_frac": round(2.0 * B * mat / step_s / FP64_MFMA_FLOPS, 4),
+               "x_batch1": round(B / step_s / b1, 2), "tokens_match": good}
+        if O is not None:
+            seeds = [1000 + s for s in seqs]
+            ctx.decode_sample_batch(seqs, first, pos0, 2, args.temperature, args.topp, seeds)     # records the sampled step of B rows
+            t0 = time.perf_counter()
+            stoks, _ = ctx.decode_sample_batch(seqs, first, pos0, steps, args.temperature, args.topp, seeds)
+            sdt = time.perf_counter() - t0
+            # the timed run's first 8 steps against the oracle's sampler fed l2_forward_batch's logits (same rows, same order)
+            rngs, toks, pos, sgood = [O.Rng(v) for v in seeds], list(first), list(pos0), True
+            for k in range(min(8, steps)):
+                lg = ctx.forward_batch(seqs, toks, pos)
+                for i in range(B):
+                    toks[i], _ = O.next_token(lg[i], args.temperature, args.topp, rngs[i])
+                    sgood = sgood and toks[i] == int(stoks[i, k])
+                    pos[i] += 1
+            ok = ok and sgood
+            sstep = sdt / steps
+            row.update({"sampled_step_ms": round(sstep * 1e3, 3), "sampled_agg_tok_s": round(B / sstep, 1),
+                        "sampled_over_greedy": round(sstep / step_s, 4), "sampled_tokens_match": sgood})
+        rows.append(row)
     res = {"tool": "batch_bench", "model": args.model, "steps": steps, "positions": "sequence s starts at 4 s (0 .. %d)" % offsets[-1],
-           "launches": "eager" if args.eager else "hipGraph", "batch1_device_loop_tok_s": round(b1, 1), "batch1_tokens_match": b1_ok, "reserved": reserved, "rows": rows, "parity": ok}
+           "launches": "eager" if args.eager else "hipGraph",
+           "sampled": None if O is None else {"temperature": args.temperature, "topp": args.topp, "seeds": "1000 + s"}, "batch1_device_loop_tok_s": round(b1, 1), "batch1_tokens_match": b1_ok, "reserved": reserved, "rows": rows, "parity": ok}
     line = json.dumps(res)
     print(line)
     if args.out:
