@@ -219,6 +219,16 @@ int l2_prefill(l2_ctx* ctx, const int32_t* tokens, int n_tokens, int pos0, float
 int l2_seq_reserve(l2_ctx* ctx, int n_seqs);
 /* l2_prefill into sequence `seq`'s cache (seq 0: exactly l2_prefill). */
 int l2_seq_prefill(l2_ctx* ctx, int seq, const int32_t* tokens, int n_tokens, int pos0, float* logits_out);
+/* Prompt ingestion for n sequences at once: sequence seqs[i] is fed n_tokens[i] tokens at positions pos0[i] .. pos0[i]+n_tokens[i]-1.
+ * tokens holds the prompts back to back, in row order.  The cache of every named sequence ends up as l2_seq_prefill would leave it.
+ * logits_out (may be NULL) receives n x V floats: row i holds the logits of sequence seqs[i]'s LAST position.
+ * The prompt rows are packed densely into launch sequences of up to 256 rows (64 on shapes the register-blocked GEMMs do not cover)
+ * that stream every weight once for all of them; a prompt may straddle launch sequences.  Blocking.  L2_E_STATE before l2_seq_reserve;
+ * L2_E_ARG for a null pointer other than logits_out, n outside [1, n_seqs], a sequence out of range or named twice, n_tokens[i] < 1,
+ * a token outside [0, vocab_size) or pos0[i] + n_tokens[i] > seq_len; L2_E_STATE for an L2_OPT_CHECK_POS skip-ahead of any sequence.
+ * A refused call writes nothing.  Sequence 0 is the context's own cache; the single-sequence state (its logits among it) is left alone. */
+int l2_seq_prefill_batch(l2_ctx* ctx, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
+                         float* logits_out);
 /* One transformer() step for each of n rows: row i feeds tokens[i] at pos[i] of sequence seqs[i] (distinct within a call).
  * Blocking.  logits_out (may be NULL) receives n x V floats, row i = that sequence's logits.  L2_E_STATE before l2_seq_reserve. */
 int l2_forward_batch(l2_ctx* ctx, int n, const int32_t* seqs, const int32_t* tokens, const int32_t* pos, float* logits_out);

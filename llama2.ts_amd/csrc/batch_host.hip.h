@@ -1,9 +1,10 @@
-// batch_host.hip.h -- host side of batched decode (batch.hip.h): l2_seq_reserve, l2_seq_prefill, l2_forward_batch,
+// batch_host.hip.h -- host side of batched decode (batch.hip.h): l2_seq_reserve, l2_seq_prefill, l2_seq_prefill_batch, l2_forward_batch,
 // l2_decode_greedy_batch, l2_decode_sample_batch, l2_read_seq_cache.
 // Part of the one translation unit llama2_hip.hip (included there, in order); not a stand-alone header.
 #pragma once
 
 enum { BT_MAX = 64 };   // rows of a batch step: four 16-row MFMA tiles
+enum { BP_ROWS = PF_S * PF_T };   // prompt rows of one packed launch sequence (l2_seq_prefill_batch)
 
 // Independent sequences sharing the context's weights.  Sequence 0's caches are the context's own (c->kc / c->vc); the others are
 // allocated by l2_seq_reserve.  The batch step has activations and tables of its own: the single-sequence state (RunState buffers,
@@ -23,6 +24,10 @@ struct BatchState {
   l2s::BatchSampler* smp = nullptr;       // the row sampler's buffers: allocated at the first l2_decode_sample_batch
   unsigned long long smp_stats[2] = {};   // {tokens sampled, of those by the serial loop} over every l2_decode_sample_batch
   std::vector<uintptr_t> sig;             // what the recorded steps baked in (weight addresses, options)
+  // Packed prompts (l2_seq_prefill_batch), allocated at its first call: activations of one launch sequence, and the call's tables
+  float *px = nullptr, *pxn = nullptr, *pq = nullptr, *pxb = nullptr, *phb = nullptr;   // [BP_ROWS][d | max(d, h) | d | d | h]
+  int* ptab = nullptr;                    // device: bp_tables' layout, ptab_cap ints
+  size_t ptab_cap = 0;
   int* seq_of() const { return tab; }
   int* tok_of() const { return tab + BT_MAX; }
   int* pos_of() const { return tab + 2 * BT_MAX; }
@@ -39,7 +44,7 @@ static void batch_free(l2_ctx* c) {
   if (!b) return;
   bt_drop_graphs(b);
   for (size_t s = 1; s < b->kc.size(); ++s) { if (b->kc[s]) hipFree(b->kc[s]); if (b->vc[s]) hipFree(b->vc[s]); }
-  void* dev[] = {b->d_kc, b->d_vc, b->tab, b->out, b->x, b->xn, b->q, b->xb, b->hb, b->logits};
+  void* dev[] = {b->d_kc, b->d_vc, b->tab, b->out, b->x, b->xn, b->q, b->xb, b->hb, b->logits, b->px, b->pxn, b->pq, b->pxb, b->phb, b->ptab};
   for (void* p : dev) if (p) hipFree(p);
   if (b->h_tab) hipHostFree(b->h_tab);
   if (b->smp) { l2s::destroy_rows(b->smp); delete b->smp; }
@@ -385,6 +390,175 @@ extern "C" int l2_seq_prefill(l2_ctx* c, int seq, const int32_t* tokens, int n_t
     HIPCHK(hipMemcpyAsync(logits_out, b->logits, (size_t)c->V * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(hipStreamSynchronize(c->stream));
+  return L2_OK;
+}
+
+// ---- packed prompts (l2_seq_prefill_batch) ------------------------------------------------------
+// The prompts of the call are packed back to back, in row order (row r of the call: its sequence, position, token), and cut into launch
+// sequences of up to BP_ROWS rows where the register-blocked GEMMs apply, else PF_T rows (the 16-row-tile kernels): prefill_chunk's
+// launch sequence over them, with the per-row q / k / v epilogue and attention over ragged tiles (batch.hip.h: bp_attn_mfma_kernel).
+// A prompt may straddle launch sequences: the later one reads the cache rows the earlier one stored.  Before the next launch sequence
+// overwrites the residual rows, those of the sequences whose LAST row lies in this one are gathered into b->x (row i: sequence seqs[i]);
+// one final norm and one classifier over those n rows give the logits.  Device tables of the call (ints), one upload:
+//   [R] sequence, [R] position, [R] token of every row; [4 x tiles] every launch sequence's BpTiles; [n] gather rows (launch-relative)
+extern "C" int l2_seq_prefill_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
+                                    float* logits_out) {
+  // ---- arguments, all checked before anything touches the GPU
+  if (!c) return fail(L2_E_ARG, "null context");
+  if (!seqs || !n_tokens || !tokens || !pos0) return fail(L2_E_ARG, "null argument");
+  if (!c->bt) return fail(L2_E_STATE, "no sequences reserved: call l2_seq_reserve first");
+  BatchState* b = c->bt;
+  if (n < 1 || n > b->n_seqs) return fail(L2_E_ARG, "n = %d outside [1, n_seqs = %d]", n, b->n_seqs);
+  bool seen[BT_MAX] = {};
+  size_t R = 0;
+  for (int i = 0; i < n; ++i) {
+    const int s = seqs[i];
+    if (s < 0 || s >= b->n_seqs) return fail(L2_E_ARG, "row %d: sequence %d outside [0, n_seqs = %d)", i, s, b->n_seqs);
+    if (seen[s]) return fail(L2_E_ARG, "row %d: sequence %d appears twice in one call", i, s);
+    seen[s] = true;
+    if (n_tokens[i] < 1) return fail(L2_E_ARG, "row %d: n_tokens %d < 1", i, n_tokens[i]);
+    if (pos0[i] < 0 || (long long)pos0[i] + n_tokens[i] > c->S)
+      return fail(L2_E_ARG, "row %d: positions %d..%lld outside [0, seq_len=%d)", i, pos0[i], (long long)pos0[i] + n_tokens[i] - 1, c->S);
+    R += (size_t)n_tokens[i];
+  }
+  for (size_t r = 0; r < R; ++r) if (tokens[r] < 0 || tokens[r] >= c->V) return fail(L2_E_ARG, "token %d (packed row %zu) outside [0, vocab_size=%d)", tokens[r], r, c->V);
+  for (int i = 0; i < n; ++i) {
+    const int s = seqs[i], next = s == 0 ? c->next_pos : b->next_pos[s];
+    if (c->opt_pos_check && pos0[i] != 0 && pos0[i] > next)
+      return fail(L2_E_STATE, "L2_CHECK_POS: sequence %d, pos %d skips ahead of the sequence (cache rows 0 .. %d have been written)", s, pos0[i], next - 1);
+  }
+  int rc = ensure_ready(c);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const size_t d = c->d, h = c->h;
+  if (!b->px) {
+    HIPCHK(hipMalloc(&b->px, BP_ROWS * d * 4)); HIPCHK(hipMalloc(&b->pxn, BP_ROWS * (d > h ? d : h) * 4));
+    HIPCHK(hipMalloc(&b->pq, BP_ROWS * d * 4)); HIPCHK(hipMalloc(&b->pxb, BP_ROWS * d * 4)); HIPCHK(hipMalloc(&b->phb, BP_ROWS * h * 4));
+    HIPCHK(hipMemset(b->pxb, 0, BP_ROWS * d * 4)); HIPCHK(hipMemset(b->pq, 0, BP_ROWS * d * 4));
+  }
+
+  // ---- the plan: rows, launch sequences, their tiles and gathers
+  const int step = pf3_ok(c) ? (int)BP_ROWS : (int)PF_T;
+  const int nl = (int)((R + step - 1) / step);
+  std::vector<size_t> first(n + 1, 0);                       // first packed row of prompt i
+  for (int i = 0; i < n; ++i) first[i + 1] = first[i] + (size_t)n_tokens[i];
+  std::vector<BpTile> tiles;
+  std::vector<int> tile0(nl + 1, 0), maxp(nl, 0), seq_a(nl, 0), seq_b(nl, 0), gsrc(n, 0);
+  for (int k = 0, i0 = 0; k < nl; ++k) {
+    const size_t r0 = (size_t)k * step, r1 = std::min(r0 + step, R);
+    tile0[k] = (int)tiles.size();
+    seq_a[k] = i0;
+    for (int i = i0; i < n && first[i] < r1; ++i) {
+      const size_t lo = std::max(first[i], r0), hi = std::min(first[i + 1], r1);
+      for (size_t t = lo; t < hi; t += 16) {      // tiles start at the run's first row in this launch sequence
+        const BpTile tl = {seqs[i], (int)(t - r0), pos0[i] + (int)(t - first[i]), (int)std::min<size_t>(16, hi - t)};
+        tiles.push_back(tl);
+        maxp[k] = std::max(maxp[k], tl.pos0);
+      }
+      if (first[i + 1] <= r1) { gsrc[i] = (int)(first[i + 1] - 1 - r0); i0 = i + 1; }      // its last row lies here
+    }
+    seq_b[k] = i0;
+    std::sort(tiles.begin() + tile0[k], tiles.end(), [](const BpTile& x, const BpTile& y) { return x.pos0 > y.pos0; });   // longest first
+  }
+  tile0[nl] = (int)tiles.size();
+  const size_t need = 3 * R + 4 * tiles.size() + (size_t)n;
+  std::vector<int> htab(need);
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < n_tokens[i]; ++k) { const size_t r = first[i] + k; htab[r] = seqs[i]; htab[R + r] = pos0[i] + k; htab[2 * R + r] = tokens[r]; }
+  if (!tiles.empty()) memcpy(htab.data() + 3 * R, tiles.data(), tiles.size() * sizeof(BpTile));
+  memcpy(htab.data() + 3 * R + 4 * tiles.size(), gsrc.data(), (size_t)n * sizeof(int));
+  if (need > b->ptab_cap) {
+    HIPCHK(hipStreamSynchronize(st));
+    if (b->ptab) { HIPCHK(hipFree(b->ptab)); b->ptab = nullptr; b->ptab_cap = 0; }
+    HIPCHK(hipMalloc(&b->ptab, need * sizeof(int)));
+    b->ptab_cap = need;
+  }
+  const int* dseq = b->ptab;
+  const int* dpos = b->ptab + R;
+  const int* dtok = b->ptab + 2 * R;
+  const BpTile* dtiles = reinterpret_cast<const BpTile*>(b->ptab + 3 * R);
+  const int* dgsrc = b->ptab + 3 * R + 4 * tiles.size();
+  HIPCHK(hipMemcpyAsync(b->ptab, htab.data(), need * sizeof(int), hipMemcpyHostToDevice, st));      // (htab lives past the final synchronise)
+
+  // ---- the launch sequences: prefill_chunk's, over the packed rows
+  for (int k = 0; k < nl; ++k) {
+    const int r0 = k * step, m = (int)std::min<size_t>(step, R - r0), nti = tile0[k + 1] - tile0[k];
+    const int chunks = (m + PF_T - 1) / PF_T;
+    const int tt = (m > 32) ? 4 : (m > 16) ? 2 : 1, nt = (chunks > 1) ? chunks * PF_T : 16 * tt;   // token rows the kernels see
+    hipLaunchKernelGGL(pf_embed_kernel, dim3(nt), dim3(256), 0, st, b->px, c->w[L2_T_TOKEN_EMBEDDING], dtok + r0, c->d, m);
+    LCHK(hipGetLastError());
+    const size_t alds = pf_attn_lds(maxp[k] + 15);      // the longest tile's keys
+    const bool mfma_attn = c->pf_attn && !c->opt_exact && (c->hs == 64 || c->hs == 128) && alds <= 150 * 1024;
+    for (int l = 0; l < c->L; ++l) {
+      const size_t loff = (size_t)l * c->S * c->d;
+      PfArgs a;
+      memset(&a, 0, sizeof(a));
+      a.fr = c->w[L2_T_FREQ_REAL]; a.fi = c->w[L2_T_FREQ_IMAG]; a.head_size = c->hs; a.dim = c->d; a.pos0 = 0; a.nvalid = m;
+      a.x = b->px;
+      a.row_seq = dseq + r0; a.row_pos = dpos + r0; a.seq_kc = b->d_kc; a.seq_vc = b->d_vc; a.seq_loff = loff;
+      // rmsnorm + q,k,v + RoPE + every row's cache row at its own (sequence, position) (llama2.ts:216-240)
+      hipLaunchKernelGGL(pf_norm_kernel, dim3(nt), dim3(256), 0, st, b->pxn, b->px, c->w[L2_T_RMS_ATT] + d * l, c->d);
+      pf_weights<MODE_QKV>(c, l, a, L2_T_WQ, L2_T_WK, L2_T_WV);
+      a.xin = b->pxn; a.out = b->pq; a.n = c->d; a.rows = 3 * c->d;
+      launch_pf_gemm<MODE_QKV_ROWS>(c, a, 4, tt, chunks, st);
+      LCHK(hipGetLastError());
+      // attention (llama2.ts:244-267): 16-query tiles on the fp64 MFMA, or the decode form per (head, row) where prefill_chunk takes it
+      if (mfma_attn) {
+        BpAttnArgs pa;
+        pa.q = b->pq; pa.xb = b->pxb; pa.seq_kc = b->d_kc; pa.seq_vc = b->d_vc; pa.seq_loff = loff; pa.tiles = dtiles + tile0[k];
+        pa.dim = c->d; pa.seq_len = c->S; pa.inv_sqrt_hs = 1.0 / sqrt((double)c->hs);
+        const dim3 grid(c->H, nti);
+        if (c->hs == 128) {
+          LCHK(lds_opt_in(&bp_attn_mfma_kernel<128>, alds));
+          hipLaunchKernelGGL((bp_attn_mfma_kernel<128>), grid, dim3(256), alds, st, pa);
+        } else {
+          LCHK(lds_opt_in(&bp_attn_mfma_kernel<64>, alds));
+          hipLaunchKernelGGL((bp_attn_mfma_kernel<64>), grid, dim3(256), alds, st, pa);
+        }
+        LCHK(hipGetLastError());
+      } else {
+        AttnArgs aa;
+        fill_attn_args(c, l, aa);      // (the kernel runs one workgroup per (head, row), one split)
+        aa.q = b->pq; aa.xb = b->pxb; aa.att = nullptr; aa.tokpos = nullptr; aa.part = nullptr; aa.counter = nullptr;
+        const AttnRows ar = {dseq + r0, dpos + r0, b->d_kc, b->d_vc, loff};
+        LCHK(launch_bt_attn(c, aa, ar, m, st));
+      }
+      // wo + residual (llama2.ts:270-273)
+      pf_weights<MODE_WO>(c, l, a, L2_T_WO, -1, -1); a.xin = b->pxb; a.n = c->d; a.rows = c->d;
+      launch_pf_gemm<MODE_WO>(c, a, 4, tt, chunks, st);
+      // rmsnorm + w1,w3 + SwiGLU (llama2.ts:276-289)
+      hipLaunchKernelGGL(pf_norm_kernel, dim3(nt), dim3(256), 0, st, b->pxn, b->px, c->w[L2_T_RMS_FFN] + d * l, c->d);
+      pf_weights<MODE_W13>(c, l, a, L2_T_W1, L2_T_W3, -1);
+      a.xin = b->pxn; a.out = b->phb; a.n = c->d; a.rows = c->h;
+      launch_pf_gemm<MODE_W13>(c, a, 4, tt, chunks, st);
+      // w2 + residual (llama2.ts:292-295)
+      pf_weights<MODE_W2>(c, l, a, L2_T_W2, -1, -1); a.xin = b->phb; a.n = c->h; a.rows = c->d;
+      launch_pf_gemm<MODE_W2>(c, a, 4, tt, chunks, st);
+      LCHK(hipGetLastError());
+    }
+    // the residual rows of the prompts that end here, into b->x rows seq_a .. seq_b - 1 (pf_embed_kernel as a row gather)
+    if (logits_out && seq_b[k] > seq_a[k]) {
+      hipLaunchKernelGGL(pf_embed_kernel, dim3(seq_b[k] - seq_a[k]), dim3(256), 0, st, b->x + (size_t)seq_a[k] * d, (const float*)b->px, dgsrc + seq_a[k],
+                         c->d, seq_b[k] - seq_a[k]);
+      LCHK(hipGetLastError());
+    }
+  }
+  if (logits_out) {      // final rmsnorm + classifier of every prompt's last row (llama2.ts:299-302)
+    hipLaunchKernelGGL(pf_norm_kernel, dim3(n), dim3(256), 0, st, b->xn, (const float*)b->x, c->w[L2_T_RMS_FINAL], c->d);
+    PfArgs a;
+    memset(&a, 0, sizeof(a));
+    bt_cls_weights(c, a);
+    a.xin = b->xn; a.out = b->logits; a.n = c->d; a.rows = c->V; a.dim = c->d; a.nvalid = n;
+    bt_gemm<MODE_CLS_ROWS>(c, a, (n > 32) ? 4 : (n > 16) ? 2 : 1, st);
+    LCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(logits_out, b->logits, (size_t)n * c->V * sizeof(float), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  for (int i = 0; i < n; ++i) {      // each sequence's next position as l2_seq_prefill leaves it
+    const int s = seqs[i], end = pos0[i] + n_tokens[i], next = s == 0 ? c->next_pos : b->next_pos[s];
+    if (end > next || pos0[i] == 0) bt_set_next(c, s, end);
+  }
   return L2_OK;
 }
 

@@ -22,8 +22,9 @@ namespace l2k {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-// GEMM modes of the batched decode step only (batch.hip.h), behind kernels.hip.h's MODE_*: q / k / v whose epilogue takes every row's
-// position and cache from device tables, and the classifier over any number of rows (the last tile's rows clamped, its stores masked)
+// GEMM modes of the batch path only (batch.hip.h), behind kernels.hip.h's MODE_*: q / k / v whose epilogue takes every row's position
+// and cache from device tables (decode steps, packed prompts), and the classifier over any number of rows (the last tile's rows clamped,
+// its stores masked)
 enum { MODE_QKV_ROWS = 5, MODE_CLS_ROWS = 6 };
 
 enum { PF_T = 64, PF_S = 4 };   // tokens per chunk: one, two or four MFMA tiles of 16; chunks per launch of the register-blocked GEMMs (blockIdx.y)
@@ -414,6 +415,7 @@ __global__ void __launch_bounds__(64 * NW) pf_gemm3_kernel(const PfArgs a_in) {
     if (a.out) a.out += (size_t)ch * PF_T * (MODE == MODE_W13 ? a.rows : a.dim);
     a.pos0 += ch * PF_T;
     a.nvalid = min(max(a.nvalid - ch * PF_T, 0), (int)PF_T);
+    if (MODE == MODE_QKV_ROWS) { a.row_seq += ch * PF_T; a.row_pos += ch * PF_T; }      // (packed prompts: every row's own sequence and position)
   }
   constexpr bool DUAL = (MODE == MODE_W13);
   constexpr int NS = DUAL ? 2 * RT : RT;             // weight streams of the wave: row tiles (w1 tile r, w3 tile r, ... when DUAL)
@@ -437,7 +439,7 @@ __global__ void __launch_bounds__(64 * NW) pf_gemm3_kernel(const PfArgs a_in) {
     const int row0 = (blockIdx.x * RT + r) * 16;
     int m = 0, i0 = row0;
     const float* wb = a.w0;
-    if (MODE == MODE_QKV) { m = row0 / a.dim; i0 = row0 - m * a.dim; wb = (m == 0) ? a.w0 : (m == 1) ? a.w1 : a.w2; }
+    if (MODE == MODE_QKV || MODE == MODE_QKV_ROWS) { m = row0 / a.dim; i0 = row0 - m * a.dim; wb = (m == 0) ? a.w0 : (m == 1) ? a.w1 : a.w2; }
     tm[r] = m; ti0[r] = i0;
     const unsigned bytes = (unsigned)16 * (unsigned)n * 4u;
     if (pk) {

@@ -30,7 +30,7 @@ static void launch_pf_gemm(const l2_ctx* c, const PfArgs& a, int nw, int tt, int
     // way) a wave takes more row tiles: q / k / v four, w1 / w3 two pairs (7B, 256 tokens: 6 510 -> 6 940 tok/s); with fewer chunks the
     // fp64 form's counts (more tiles per wave at 128 tokens left CUs idle: 5 520 -> 4 910)
     const int tiles = a.rows / 16;
-    if constexpr (MODE == MODE_QKV) { if (chunks == 4 && tiles % 4 == 0) launch_pf3<MODE, 4, true>(a, chunks, st); else launch_pf3<MODE, 3, true>(a, chunks, st); return; }
+    if constexpr (MODE == MODE_QKV || MODE == MODE_QKV_ROWS) { if (chunks == 4 && tiles % 4 == 0) launch_pf3<MODE, 4, true>(a, chunks, st); else launch_pf3<MODE, 3, true>(a, chunks, st); return; }
     else if constexpr (MODE == MODE_W13) { if (chunks == 4 && tiles % 2 == 0) launch_pf3<MODE, 2, true>(a, chunks, st); else launch_pf3<MODE, 1, true>(a, chunks, st); return; }
     else {
       if (chunks == 4 && tiles % 4 == 0) launch_pf3<MODE, 4, true>(a, chunks, st);
@@ -42,7 +42,7 @@ static void launch_pf_gemm(const l2_ctx* c, const PfArgs& a, int nw, int tt, int
   if (pf3_ok(c) && tt == 4) {
     // row tiles per wave: conversions per MFMA are 16 (R + 64) / (64 R) for R rows per workgroup, so as many as still leave >= 256
     // workgroups: qkv 3 (3 d / 16 tiles), w1 / w3 one pair (688 pairs at 7B), wo / w2 (d / 16 tiles) 1, 2 or 4 with the chunk count
-    if constexpr (MODE == MODE_QKV) { launch_pf3<MODE, 3>(a, chunks, st); return; }
+    if constexpr (MODE == MODE_QKV || MODE == MODE_QKV_ROWS) { launch_pf3<MODE, 3>(a, chunks, st); return; }      // (QKV_ROWS: packed prompts, batch_host.hip.h)
     else if constexpr (MODE == MODE_W13) { launch_pf3<MODE, 1>(a, chunks, st); return; }
     else {
       const int tiles = a.rows / 16;

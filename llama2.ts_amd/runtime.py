@@ -37,7 +37,7 @@ ABI_SYMBOLS = ["l2_abi_version", "l2_device_count", "l2_last_error", "l2_create"
                "l2_decode_greedy", "l2_decode_sample", "l2_debug_running_sums", "l2_read_state", "l2_set_option", "l2_get_option", "l2_timer_start",
                "l2_timer_stop", "l2_bench_gemv", "l2_bench_decode", "l2_load_checkpoint", "l2_get_header", "l2_prefill", "l2_bench_dominant_in_situ", "l2_tp_mode", "l2_create_ex", "l2_bench_tokens", "l2_dispatch_reason",
                "l2_seq_reserve", "l2_seq_prefill", "l2_forward_batch", "l2_decode_greedy_batch", "l2_read_seq_cache",
-               "l2_decode_sample_batch"]
+               "l2_decode_sample_batch", "l2_seq_prefill_batch"]
 
 
 class L2Error(RuntimeError):
@@ -98,6 +98,7 @@ def lib():
     L.l2_decode_greedy_batch.argtypes = [vp, i32, vp, vp, vp, i32, vp]
     L.l2_read_seq_cache.argtypes = [vp, i32, i32, i32, vp, sz]
     L.l2_decode_sample_batch.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.l2_seq_prefill_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     for name in ABI_SYMBOLS:   # fail at load time, not at first use, if the .so is stale
         getattr(L, name)
     _lib = L
@@ -248,6 +249,21 @@ class Context:
         t = np.ascontiguousarray(tokens, dtype=np.int32)
         out = np.empty(self.cfg.vocab_size, dtype=np.float32)
         _check(lib().l2_seq_prefill(self._h, int(seq), t.ctypes.data, t.size, int(pos0), out.ctypes.data))
+        return out
+
+    def seq_prefill_batch(self, seqs, prompts, pos0=0):
+        """Feed prompts[i] into sequence seqs[i] at pos0[i].. for every i in one packed call; returns the (n, V) logits of every
+        prompt's last position.  pos0: a scalar or one per prompt."""
+        s = np.ascontiguousarray(seqs, dtype=np.int32).reshape(-1)
+        ps = [np.ascontiguousarray(p, dtype=np.int32).reshape(-1) for p in prompts]
+        if len(ps) != s.size:
+            raise ValueError("one prompt per sequence")
+        p0 = np.ascontiguousarray(np.broadcast_to(np.asarray(pos0, dtype=np.int32), (s.size,)))
+        nt = np.array([p.size for p in ps], dtype=np.int32)
+        tok = np.ascontiguousarray(np.concatenate(ps) if ps else np.zeros(0, dtype=np.int32), dtype=np.int32)
+        out = np.empty((s.size, self.cfg.vocab_size), dtype=np.float32)
+        _check(lib().l2_seq_prefill_batch(self._h, s.size, s.ctypes.data, nt.ctypes.data, tok.ctypes.data, p0.ctypes.data,
+                                          out.ctypes.data))
         return out
 
     @staticmethod
