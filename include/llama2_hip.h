@@ -27,7 +27,8 @@ extern "C" {
  * 5 (round 6): option keys L2_OPT_PREFILL_F32_MFMA, L2_OPT_CHECK_POS; l2_dispatch_reason
  * The batched decode of independent sequences (l2_seq_reserve .. l2_read_seq_cache, option key L2_OPT_SEQS) joined the surface without a
  * version step: it only adds, and a binding detects it by the presence of the l2_seq_reserve symbol.  So did its sampled loop
- * (l2_decode_sample_batch, option keys L2_OPT_BATCH_SAMPLED_TOKENS / _SERIAL), detected by its own symbol. */
+ * (l2_decode_sample_batch, option keys L2_OPT_BATCH_SAMPLED_TOKENS / _SERIAL), detected by its own symbol, and so were the packed
+ * prompts (l2_seq_prefill_batch) and the mixed step (l2_step_batch). */
 #define L2_ABI_VERSION 5
 
 enum {
@@ -100,7 +101,7 @@ enum {
                                  496) and attention reads whatever rows 0 .. pos - 1 the cache holds; 0 (default): any position is accepted.
                                  Applies per sequence to the batch calls below (sequence 0 shares its position with l2_forward / l2_prefill) */
   L2_OPT_SEQS = 11,           /* read-only: sequences reserved by l2_seq_reserve (0 before it) */
-  L2_OPT_BATCH_SAMPLED_TOKENS = 12, /* read-only: tokens l2_decode_sample_batch has sampled (temperature != 0), saturating */
+  L2_OPT_BATCH_SAMPLED_TOKENS = 12, /* read-only: tokens l2_decode_sample_batch and l2_step_batch have sampled (temperature != 0), saturating */
   L2_OPT_BATCH_SAMPLED_SERIAL = 13  /* read-only: of those, the ones the margin form's serial loop picked */
 };
 
@@ -248,6 +249,21 @@ int l2_decode_greedy_batch(l2_ctx* ctx, int n, const int32_t* seqs, const int32_
  * state and L2_OPT_SAMPLED_TOKENS / _SERIAL are left alone. */
 int l2_decode_sample_batch(l2_ctx* ctx, int n, const int32_t* seqs, const int32_t* first_tokens, const int32_t* pos0, int steps,
                            const double* temperature, const double* topp, uint64_t* rng_state, int32_t* tokens_out);
+/* One mixed step of continuous batching: decode rows and prompt chunks in one call, one pick per row made on the device.  Sequence
+ * seqs[i] is fed n_tokens[i] tokens at positions pos0[i] .. pos0[i]+n_tokens[i]-1, exactly as l2_seq_prefill_batch feeds them (tokens
+ * back to back in row order; every cache ends as l2_seq_prefill would leave it).  Then row i makes ONE pick from the logits of its run's
+ * last position, by the rules of l2_decode_sample_batch: temperature[i] == 0 takes the argmax (no draw, rng_state[i] left alone),
+ * otherwise logits / temperature[i], softmax, then `sample` or `sample_topp` with one xorshift* draw from rng_state[i].  temperature,
+ * topp and rng_state all NULL: every row greedy.  picks_out (n ints) is required; logits_out (may be NULL) receives n x V floats, row
+ * i = the unscaled logits row i's pick was made from; rng_state is written back only on success.  Runs of one row (decode rows) take
+ * the decode attention form per (head, row) at any head size and position, runs of two or more the prompt path's 16-query tiles.
+ * Blocking, eager launches on the context's stream.  Argument rules of l2_seq_prefill_batch, plus: L2_E_ARG for a null picks_out, some
+ * but not all of temperature / topp / rng_state NULL, or a NaN setting; L2_E_CONFIG when a row samples and vocab_size exceeds the
+ * device sampler's limit.  A refused call writes nothing.  L2_OPT_EXACT_ATTENTION, L2_OPT_PREFILL_F32_MFMA, L2_OPT_CHECK_POS and the
+ * L2_SAMPLER_FORCE_SERIAL test hook apply; sampled tokens count into L2_OPT_BATCH_SAMPLED_TOKENS / _SERIAL.  Sequence 0 is the
+ * context's own cache; the single-sequence state is left alone. */
+int l2_step_batch(l2_ctx* ctx, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
+                  const double* temperature, const double* topp, uint64_t* rng_state, int32_t* picks_out, float* logits_out);
 /* Read sequence `seq`'s key / value cache (which = L2_S_KEY_CACHE / L2_S_VALUE_CACHE; layer -1 = all), like l2_read_state. */
 int l2_read_seq_cache(l2_ctx* ctx, int seq, int which, int layer, float* out, size_t n_floats);
 

@@ -1,5 +1,5 @@
 // batch_host.hip.h -- host side of batched decode (batch.hip.h): l2_seq_reserve, l2_seq_prefill, l2_seq_prefill_batch, l2_forward_batch,
-// l2_decode_greedy_batch, l2_decode_sample_batch, l2_read_seq_cache.
+// l2_decode_greedy_batch, l2_decode_sample_batch, l2_step_batch, l2_read_seq_cache.
 // Part of the one translation unit llama2_hip.hip (included there, in order); not a stand-alone header.
 #pragma once
 
@@ -310,6 +310,17 @@ extern "C" int l2_decode_greedy_batch(l2_ctx* c, int n, const int32_t* seqs, con
   return L2_OK;
 }
 
+// The row sampler's buffers (one row per reserved sequence), allocated at the first call that samples.
+static int bt_ensure_sampler(l2_ctx* c, const char* who) {
+  BatchState* b = c->bt;
+  if (b->smp) return L2_OK;
+  l2s::BatchSampler* sm = new l2s::BatchSampler();
+  const hipError_t e = l2s::create_rows(sm, c->V, b->n_seqs);
+  if (e != hipSuccess) { delete sm; (void)hipGetLastError(); return fail(L2_E_HIP, "%s: device memory for the row sampler: %s", who, hipGetErrorString(e)); }
+  b->smp = sm;
+  return L2_OK;
+}
+
 extern "C" int l2_decode_sample_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_t* first_tokens, const int32_t* pos0, int steps,
                                       const double* temperature, const double* topp, uint64_t* rng_state, int32_t* tokens_out) {
   int rc = bt_check(c, n, seqs, first_tokens, pos0, steps);
@@ -331,12 +342,8 @@ extern "C" int l2_decode_sample_batch(l2_ctx* c, int n, const int32_t* seqs, con
     return L2_OK;
   }
   HIPCHK(hipSetDevice(c->device));
-  if (!b->smp) {
-    l2s::BatchSampler* sm = new l2s::BatchSampler();
-    const hipError_t e = l2s::create_rows(sm, c->V, b->n_seqs);
-    if (e != hipSuccess) { delete sm; (void)hipGetLastError(); return fail(L2_E_HIP, "l2_decode_sample_batch: device memory for the row sampler: %s", hipGetErrorString(e)); }
-    b->smp = sm;
-  }
+  rc = bt_ensure_sampler(c, "l2_decode_sample_batch");
+  if (rc) return rc;
   l2s::BatchSampler& sm = *b->smp;
   HIPCHK(hipStreamSynchronize(c->stream));      // (the pinned tables: the previous call's copies have completed)
   for (int i = 0; i < n; ++i) { sm.h_params[2 * i] = temperature[i]; sm.h_params[2 * i + 1] = topp[i]; sm.h_rng[i] = rng_state[i]; }
@@ -393,17 +400,17 @@ extern "C" int l2_seq_prefill(l2_ctx* c, int seq, const int32_t* tokens, int n_t
   return L2_OK;
 }
 
-// ---- packed prompts (l2_seq_prefill_batch) ------------------------------------------------------
-// The prompts of the call are packed back to back, in row order (row r of the call: its sequence, position, token), and cut into launch
-// sequences of up to BP_ROWS rows where the register-blocked GEMMs apply, else PF_T rows (the 16-row-tile kernels): prefill_chunk's
-// launch sequence over them, with the per-row q / k / v epilogue and attention over ragged tiles (batch.hip.h: bp_attn_mfma_kernel).
-// A prompt may straddle launch sequences: the later one reads the cache rows the earlier one stored.  Before the next launch sequence
-// overwrites the residual rows, those of the sequences whose LAST row lies in this one are gathered into b->x (row i: sequence seqs[i]);
-// one final norm and one classifier over those n rows give the logits.  Device tables of the call (ints), one upload:
+// ---- packed prompts (l2_seq_prefill_batch) and the mixed step (l2_step_batch) -----------------
+// The runs of a call are packed back to back, in packing order (row r: its sequence, position, token), and cut into launch sequences of up
+// to BP_ROWS rows where the register-blocked GEMMs apply, else PF_T rows (the 16-row-tile kernels): prefill_chunk's launch sequence over
+// them, with the per-row q / k / v epilogue and attention over ragged tiles (batch.hip.h: bp_attn_mfma_kernel).  A run may straddle
+// launch sequences: the later one reads the cache rows the earlier one stored.  Before the next launch sequence overwrites the residual
+// rows, those of the runs whose LAST row lies in this one are gathered into b->x (row i: run i); one final norm and one classifier over
+// those n rows give the logits.  Device tables of the call (ints), one upload:
 //   [R] sequence, [R] position, [R] token of every row; [4 x tiles] every launch sequence's BpTiles; [n] gather rows (launch-relative)
-extern "C" int l2_seq_prefill_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
-                                    float* logits_out) {
-  // ---- arguments, all checked before anything touches the GPU
+
+// Arguments of a packed call, all checked before anything touches the GPU; *R_out: the packed rows.
+static int bp_check(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0, size_t* R_out) {
   if (!c) return fail(L2_E_ARG, "null context");
   if (!seqs || !n_tokens || !tokens || !pos0) return fail(L2_E_ARG, "null argument");
   if (!c->bt) return fail(L2_E_STATE, "no sequences reserved: call l2_seq_reserve first");
@@ -427,9 +434,18 @@ extern "C" int l2_seq_prefill_batch(l2_ctx* c, int n, const int32_t* seqs, const
     if (c->opt_pos_check && pos0[i] != 0 && pos0[i] > next)
       return fail(L2_E_STATE, "L2_CHECK_POS: sequence %d, pos %d skips ahead of the sequence (cache rows 0 .. %d have been written)", s, pos0[i], next - 1);
   }
-  int rc = ensure_ready(c);
-  if (rc) return rc;
-  HIPCHK(hipSetDevice(c->device));
+  *R_out = R;
+  return L2_OK;
+}
+
+// Enqueue the launch sequences of n checked runs given in packing order (R rows in all).  The first nd runs are decode rows (one row
+// each, l2_step_batch; 0 for l2_seq_prefill_batch): they lie in the first launch sequence, are cut into no tile, and take the decode
+// attention form per (head, row) -- bt_attn_tile_kernel, at any head size and position -- while the tiles of the longer runs take
+// bp_attn_mfma_kernel with its LDS sized by the longest of them.  `logits`: gather every run's last row, final norm and classifier ->
+// b->logits rows 0 .. n-1.  htab holds the uploaded tables: the caller keeps it until the stream has been synchronised.
+static int bp_enqueue(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0, size_t R, int nd,
+                      bool logits, std::vector<int>& htab) {
+  BatchState* b = c->bt;
   hipStream_t st = c->stream;
   const size_t d = c->d, h = c->h;
   if (!b->px) {
@@ -441,7 +457,7 @@ extern "C" int l2_seq_prefill_batch(l2_ctx* c, int n, const int32_t* seqs, const
   // ---- the plan: rows, launch sequences, their tiles and gathers
   const int step = pf3_ok(c) ? (int)BP_ROWS : (int)PF_T;
   const int nl = (int)((R + step - 1) / step);
-  std::vector<size_t> first(n + 1, 0);                       // first packed row of prompt i
+  std::vector<size_t> first(n + 1, 0);                       // first packed row of run i
   for (int i = 0; i < n; ++i) first[i + 1] = first[i] + (size_t)n_tokens[i];
   std::vector<BpTile> tiles;
   std::vector<int> tile0(nl + 1, 0), maxp(nl, 0), seq_a(nl, 0), seq_b(nl, 0), gsrc(n, 0);
@@ -451,7 +467,7 @@ extern "C" int l2_seq_prefill_batch(l2_ctx* c, int n, const int32_t* seqs, const
     seq_a[k] = i0;
     for (int i = i0; i < n && first[i] < r1; ++i) {
       const size_t lo = std::max(first[i], r0), hi = std::min(first[i + 1], r1);
-      for (size_t t = lo; t < hi; t += 16) {      // tiles start at the run's first row in this launch sequence
+      for (size_t t = lo; t < hi && i >= nd; t += 16) {      // tiles start at the run's first row in this launch sequence
         const BpTile tl = {seqs[i], (int)(t - r0), pos0[i] + (int)(t - first[i]), (int)std::min<size_t>(16, hi - t)};
         tiles.push_back(tl);
         maxp[k] = std::max(maxp[k], tl.pos0);
@@ -463,7 +479,7 @@ extern "C" int l2_seq_prefill_batch(l2_ctx* c, int n, const int32_t* seqs, const
   }
   tile0[nl] = (int)tiles.size();
   const size_t need = 3 * R + 4 * tiles.size() + (size_t)n;
-  std::vector<int> htab(need);
+  htab.assign(need, 0);
   for (int i = 0; i < n; ++i)
     for (int k = 0; k < n_tokens[i]; ++k) { const size_t r = first[i] + k; htab[r] = seqs[i]; htab[R + r] = pos0[i] + k; htab[2 * R + r] = tokens[r]; }
   if (!tiles.empty()) memcpy(htab.data() + 3 * R, tiles.data(), tiles.size() * sizeof(BpTile));
@@ -479,11 +495,12 @@ extern "C" int l2_seq_prefill_batch(l2_ctx* c, int n, const int32_t* seqs, const
   const int* dtok = b->ptab + 2 * R;
   const BpTile* dtiles = reinterpret_cast<const BpTile*>(b->ptab + 3 * R);
   const int* dgsrc = b->ptab + 3 * R + 4 * tiles.size();
-  HIPCHK(hipMemcpyAsync(b->ptab, htab.data(), need * sizeof(int), hipMemcpyHostToDevice, st));      // (htab lives past the final synchronise)
+  HIPCHK(hipMemcpyAsync(b->ptab, htab.data(), need * sizeof(int), hipMemcpyHostToDevice, st));      // (htab lives past the caller's synchronise)
 
   // ---- the launch sequences: prefill_chunk's, over the packed rows
   for (int k = 0; k < nl; ++k) {
     const int r0 = k * step, m = (int)std::min<size_t>(step, R - r0), nti = tile0[k + 1] - tile0[k];
+    const int ndk = k == 0 ? nd : 0;                           // decode rows of this launch sequence (its rows 0 .. ndk-1)
     const int chunks = (m + PF_T - 1) / PF_T;
     const int tt = (m > 32) ? 4 : (m > 16) ? 2 : 1, nt = (chunks > 1) ? chunks * PF_T : 16 * tt;   // token rows the kernels see
     hipLaunchKernelGGL(pf_embed_kernel, dim3(nt), dim3(256), 0, st, b->px, c->w[L2_T_TOKEN_EMBEDDING], dtok + r0, c->d, m);
@@ -503,20 +520,30 @@ extern "C" int l2_seq_prefill_batch(l2_ctx* c, int n, const int32_t* seqs, const
       a.xin = b->pxn; a.out = b->pq; a.n = c->d; a.rows = 3 * c->d;
       launch_pf_gemm<MODE_QKV_ROWS>(c, a, 4, tt, chunks, st);
       LCHK(hipGetLastError());
-      // attention (llama2.ts:244-267): 16-query tiles on the fp64 MFMA, or the decode form per (head, row) where prefill_chunk takes it
+      // attention (llama2.ts:244-267): 16-query tiles on the fp64 MFMA (decode rows: per (head, row)), or the decode form per (head, row)
+      // for every row where prefill_chunk takes it
       if (mfma_attn) {
-        BpAttnArgs pa;
-        pa.q = b->pq; pa.xb = b->pxb; pa.seq_kc = b->d_kc; pa.seq_vc = b->d_vc; pa.seq_loff = loff; pa.tiles = dtiles + tile0[k];
-        pa.dim = c->d; pa.seq_len = c->S; pa.inv_sqrt_hs = 1.0 / sqrt((double)c->hs);
-        const dim3 grid(c->H, nti);
-        if (c->hs == 128) {
-          LCHK(lds_opt_in(&bp_attn_mfma_kernel<128>, alds));
-          hipLaunchKernelGGL((bp_attn_mfma_kernel<128>), grid, dim3(256), alds, st, pa);
-        } else {
-          LCHK(lds_opt_in(&bp_attn_mfma_kernel<64>, alds));
-          hipLaunchKernelGGL((bp_attn_mfma_kernel<64>), grid, dim3(256), alds, st, pa);
+        if (ndk > 0) {
+          AttnArgs aa;
+          fill_attn_args(c, l, aa);      // (the kernel runs one workgroup per (head, row), one split)
+          aa.q = b->pq; aa.xb = b->pxb; aa.att = nullptr; aa.tokpos = nullptr; aa.part = nullptr; aa.counter = nullptr;
+          const AttnRows ar = {dseq + r0, dpos + r0, b->d_kc, b->d_vc, loff};
+          LCHK(launch_bt_attn(c, aa, ar, ndk, st));
         }
-        LCHK(hipGetLastError());
+        if (nti > 0) {
+          BpAttnArgs pa;
+          pa.q = b->pq; pa.xb = b->pxb; pa.seq_kc = b->d_kc; pa.seq_vc = b->d_vc; pa.seq_loff = loff; pa.tiles = dtiles + tile0[k];
+          pa.dim = c->d; pa.seq_len = c->S; pa.inv_sqrt_hs = 1.0 / sqrt((double)c->hs);
+          const dim3 grid(c->H, nti);
+          if (c->hs == 128) {
+            LCHK(lds_opt_in(&bp_attn_mfma_kernel<128>, alds));
+            hipLaunchKernelGGL((bp_attn_mfma_kernel<128>), grid, dim3(256), alds, st, pa);
+          } else {
+            LCHK(lds_opt_in(&bp_attn_mfma_kernel<64>, alds));
+            hipLaunchKernelGGL((bp_attn_mfma_kernel<64>), grid, dim3(256), alds, st, pa);
+          }
+          LCHK(hipGetLastError());
+        }
       } else {
         AttnArgs aa;
         fill_attn_args(c, l, aa);      // (the kernel runs one workgroup per (head, row), one split)
@@ -537,14 +564,14 @@ extern "C" int l2_seq_prefill_batch(l2_ctx* c, int n, const int32_t* seqs, const
       launch_pf_gemm<MODE_W2>(c, a, 4, tt, chunks, st);
       LCHK(hipGetLastError());
     }
-    // the residual rows of the prompts that end here, into b->x rows seq_a .. seq_b - 1 (pf_embed_kernel as a row gather)
-    if (logits_out && seq_b[k] > seq_a[k]) {
+    // the residual rows of the runs that end here, into b->x rows seq_a .. seq_b - 1 (pf_embed_kernel as a row gather)
+    if (logits && seq_b[k] > seq_a[k]) {
       hipLaunchKernelGGL(pf_embed_kernel, dim3(seq_b[k] - seq_a[k]), dim3(256), 0, st, b->x + (size_t)seq_a[k] * d, (const float*)b->px, dgsrc + seq_a[k],
                          c->d, seq_b[k] - seq_a[k]);
       LCHK(hipGetLastError());
     }
   }
-  if (logits_out) {      // final rmsnorm + classifier of every prompt's last row (llama2.ts:299-302)
+  if (logits) {      // final rmsnorm + classifier of every run's last row (llama2.ts:299-302)
     hipLaunchKernelGGL(pf_norm_kernel, dim3(n), dim3(256), 0, st, b->xn, (const float*)b->x, c->w[L2_T_RMS_FINAL], c->d);
     PfArgs a;
     memset(&a, 0, sizeof(a));
@@ -552,13 +579,124 @@ extern "C" int l2_seq_prefill_batch(l2_ctx* c, int n, const int32_t* seqs, const
     a.xin = b->xn; a.out = b->logits; a.n = c->d; a.rows = c->V; a.dim = c->d; a.nvalid = n;
     bt_gemm<MODE_CLS_ROWS>(c, a, (n > 32) ? 4 : (n > 16) ? 2 : 1, st);
     LCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(logits_out, b->logits, (size_t)n * c->V * sizeof(float), hipMemcpyDeviceToHost, st));
   }
-  HIPCHK(hipStreamSynchronize(st));
-  for (int i = 0; i < n; ++i) {      // each sequence's next position as l2_seq_prefill leaves it
-    const int s = seqs[i], end = pos0[i] + n_tokens[i], next = s == 0 ? c->next_pos : b->next_pos[s];
+  return L2_OK;
+}
+
+// Each named sequence's next position as l2_seq_prefill leaves it (after the stream has been synchronised).
+static void bp_set_next(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* pos0) {
+  for (int i = 0; i < n; ++i) {
+    const int s = seqs[i], end = pos0[i] + n_tokens[i], next = s == 0 ? c->next_pos : c->bt->next_pos[s];
     if (end > next || pos0[i] == 0) bt_set_next(c, s, end);
   }
+}
+
+extern "C" int l2_seq_prefill_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
+                                    float* logits_out) {
+  size_t R = 0;
+  int rc = bp_check(c, n, seqs, n_tokens, tokens, pos0, &R);
+  if (rc) return rc;
+  rc = ensure_ready(c);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  std::vector<int> htab;
+  rc = bp_enqueue(c, n, seqs, n_tokens, tokens, pos0, R, 0, logits_out != nullptr, htab);
+  if (rc) return rc;
+  if (logits_out) HIPCHK(hipMemcpyAsync(logits_out, c->bt->logits, (size_t)n * c->V * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  bp_set_next(c, n, seqs, n_tokens, pos0);
+  return L2_OK;
+}
+
+// ---- the mixed step (l2_step_batch) --------------------------------------------------------------
+// The runs are reordered so that the one-row runs (decode rows) come first, then packed and run as above; every run's last-position
+// logits then get one pick on the device: bt_argmax_kernel when no row samples, else the row sampler's phases and bt_pick_kernel.  The
+// picks land in the batch step's token table (its position and start columns zeroed first, so each row's pick is also out[r][0]); only
+// they, the rng states and the optional logits come back.
+extern "C" int l2_step_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
+                             const double* temperature, const double* topp, uint64_t* rng_state, int32_t* picks_out, float* logits_out) {
+  size_t R = 0;
+  int rc = bp_check(c, n, seqs, n_tokens, tokens, pos0, &R);
+  if (rc) return rc;
+  if (!picks_out) return fail(L2_E_ARG, "null picks_out");
+  const int given = (temperature != nullptr) + (topp != nullptr) + (rng_state != nullptr);
+  if (given != 0 && given != 3) return fail(L2_E_ARG, "temperature / topp / rng_state: give all three, or none for every row greedy");
+  bool any = false;
+  for (int i = 0; given && i < n; ++i) {
+    if (!(temperature[i] == temperature[i]) || !(topp[i] == topp[i])) return fail(L2_E_ARG, "row %d: temperature / topp is NaN", i);
+    if (temperature[i] != 0.0) any = true;
+  }
+  if (any && c->V > l2s::MAX_VOCAB) return fail(L2_E_CONFIG, "device sampler supports vocabularies up to %d", (int)l2s::MAX_VOCAB);
+
+  // packing order: decode rows (runs of one row) first, then the longer runs, each group in call order
+  std::vector<int> ord;
+  ord.reserve(n);
+  for (int i = 0; i < n; ++i) if (n_tokens[i] == 1) ord.push_back(i);
+  const int nd = (int)ord.size();
+  for (int i = 0; i < n; ++i) if (n_tokens[i] > 1) ord.push_back(i);
+  std::vector<size_t> first(n + 1, 0);
+  for (int i = 0; i < n; ++i) first[i + 1] = first[i] + (size_t)n_tokens[i];
+  std::vector<int32_t> ps(n), pn(n), pp(n), ptok;
+  ptok.reserve(R);
+  bool identity = true;
+  for (int j = 0; j < n; ++j) {
+    const int i = ord[j];
+    identity = identity && i == j;
+    ps[j] = seqs[i]; pn[j] = n_tokens[i]; pp[j] = pos0[i];
+    ptok.insert(ptok.end(), tokens + first[i], tokens + first[i + 1]);
+  }
+
+  rc = ensure_ready(c);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  BatchState* b = c->bt;
+  hipStream_t st = c->stream;
+  if (any) {
+    rc = bt_ensure_sampler(c, "l2_step_batch");
+    if (rc) return rc;
+  }
+  HIPCHK(hipStreamSynchronize(st));      // (the pinned tables: the previous call's copies have completed)
+  std::vector<int> htab;
+  rc = bp_enqueue(c, n, ps.data(), pn.data(), ptok.data(), pp.data(), R, nd, true, htab);
+  if (rc) return rc;
+  HIPCHK(hipMemsetAsync(b->tab, 0, 4 * BT_MAX * sizeof(int), st));
+  if (any) {
+    l2s::BatchSampler& sm = *b->smp;
+    for (int j = 0; j < n; ++j) { sm.h_params[2 * j] = temperature[ord[j]]; sm.h_params[2 * j + 1] = topp[ord[j]]; sm.h_rng[j] = rng_state[ord[j]]; }
+    HIPCHK(l2s::reset_rows(sm, n, st));
+    HIPCHK(hipMemcpyAsync(sm.params, sm.h_params, 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sm.rng, sm.h_rng, (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    LCHK(l2s::enqueue_rows(sm, b->logits, n, st));
+    hipLaunchKernelGGL(bt_pick_kernel, dim3(n), dim3(1024), 0, st, (const float*)b->logits, c->V, (const double*)sm.params, sm.pick,
+                       b->tok_of(), b->pos_of(), (const int*)b->start_of(), b->out, c->S);
+  } else {
+    hipLaunchKernelGGL(bt_argmax_kernel, dim3(n), dim3(1024), 0, st, (const float*)b->logits, c->V, b->tok_of(), b->pos_of(), (const int*)b->start_of(),
+                       b->out, c->S);
+  }
+  LCHK(hipGetLastError());
+  std::vector<int32_t> picks(n);
+  HIPCHK(hipMemcpyAsync(picks.data(), b->tok_of(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  std::vector<float> lg;
+  if (logits_out) {
+    float* dst = logits_out;
+    if (!identity) { lg.resize((size_t)n * c->V); dst = lg.data(); }
+    HIPCHK(hipMemcpyAsync(dst, b->logits, (size_t)n * c->V * sizeof(float), hipMemcpyDeviceToHost, st));
+  }
+  if (any) {
+    HIPCHK(hipMemcpyAsync(b->smp->h_rng, b->smp->rng, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(b->smp->h_stats, b->smp->stats, 2 * (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  for (int j = 0; j < n; ++j) {
+    const int i = ord[j];
+    picks_out[i] = picks[j];
+    if (!lg.empty()) memcpy(logits_out + (size_t)i * c->V, lg.data() + (size_t)j * c->V, (size_t)c->V * sizeof(float));
+    if (any) {
+      rng_state[i] = b->smp->h_rng[j];
+      for (int k = 0; k < 2; ++k) { const unsigned long long v = b->smp_stats[k] + b->smp->h_stats[2 * j + k]; b->smp_stats[k] = v < b->smp_stats[k] ? ~0ull : v; }
+    }
+  }
+  bp_set_next(c, n, seqs, n_tokens, pos0);
   return L2_OK;
 }
 

@@ -27,7 +27,7 @@ STATE_IDS = dict(x=S_X, xb=S_XB, xb2=S_XB2, hb=S_HB, hb2=S_HB2, q=S_Q, k=S_K, v=
                  key_cache=S_KEY_CACHE, value_cache=S_VALUE_CACHE)
 OPT_EXACT_ATTENTION, OPT_USE_GRAPH, OPT_KEEP_STATE, OPT_PACKED_MIB, OPT_WEIGHT_MIB, OPT_SAMPLED_TOKENS, OPT_SAMPLED_SERIAL, OPT_AQL_QUEUE, OPT_PREFILL_F32_MFMA, OPT_CHECK_POS = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 OPT_SEQS = 11      # read-only: sequences reserved by seq_reserve (0 before it)
-OPT_BATCH_SAMPLED_TOKENS, OPT_BATCH_SAMPLED_SERIAL = 12, 13   # read-only: decode_sample_batch's sampled tokens, of those by the serial loop
+OPT_BATCH_SAMPLED_TOKENS, OPT_BATCH_SAMPLED_SERIAL = 12, 13   # read-only: decode_sample_batch's and step_batch's sampled tokens, of those by the serial loop
 F_GQA, F_GENERATE_ROPE = 1, 2     # l2_create_ex flags
 TP_SOLO_ID = b"L2-SOLO-SHARD-TIMING"   # l2_create_tp id of a shard-timing context (include/llama2_hip.h: L2_TP_SOLO_ID)
 
@@ -37,7 +37,7 @@ ABI_SYMBOLS = ["l2_abi_version", "l2_device_count", "l2_last_error", "l2_create"
                "l2_decode_greedy", "l2_decode_sample", "l2_debug_running_sums", "l2_read_state", "l2_set_option", "l2_get_option", "l2_timer_start",
                "l2_timer_stop", "l2_bench_gemv", "l2_bench_decode", "l2_load_checkpoint", "l2_get_header", "l2_prefill", "l2_bench_dominant_in_situ", "l2_tp_mode", "l2_create_ex", "l2_bench_tokens", "l2_dispatch_reason",
                "l2_seq_reserve", "l2_seq_prefill", "l2_forward_batch", "l2_decode_greedy_batch", "l2_read_seq_cache",
-               "l2_decode_sample_batch", "l2_seq_prefill_batch"]
+               "l2_decode_sample_batch", "l2_seq_prefill_batch", "l2_step_batch"]
 
 
 class L2Error(RuntimeError):
@@ -99,6 +99,7 @@ def lib():
     L.l2_read_seq_cache.argtypes = [vp, i32, i32, i32, vp, sz]
     L.l2_decode_sample_batch.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]
     L.l2_seq_prefill_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.l2_step_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     for name in ABI_SYMBOLS:   # fail at load time, not at first use, if the .so is stale
         getattr(L, name)
     _lib = L
@@ -265,6 +266,38 @@ class Context:
         _check(lib().l2_seq_prefill_batch(self._h, s.size, s.ctypes.data, nt.ctypes.data, tok.ctypes.data, p0.ctypes.data,
                                           out.ctypes.data))
         return out
+
+    def step_batch(self, seqs, runs, pos0, temperature=0.0, topp=1.0, rng=None, logits=False):
+        """One mixed step: feed runs[i] into sequence seqs[i] at pos0[i].. (a run of one token is a decode row), then one pick per row
+        from its run's last-position logits, made on the device (temperature 0: argmax, no draw; else one xorshift* draw from rng[i]).
+        temperature / topp: a scalar or one per row; rng: one state per row (uint64), or None when every row is greedy.  Returns
+        (picks, rng_after[, (n, V) logits the picks were made from])."""
+        s = np.ascontiguousarray(seqs, dtype=np.int32).reshape(-1)
+        n = s.size
+        rs = [np.ascontiguousarray(r, dtype=np.int32).reshape(-1) for r in runs]
+        if len(rs) != n:
+            raise ValueError("one run per sequence")
+        p0 = np.ascontiguousarray(np.broadcast_to(np.asarray(pos0, dtype=np.int32), (n,)))
+        nt = np.array([r.size for r in rs], dtype=np.int32)
+        tok = np.ascontiguousarray(np.concatenate(rs) if rs else np.zeros(0, dtype=np.int32), dtype=np.int32)
+        picks = np.zeros(n, dtype=np.int32)
+        out = np.empty((n, self.cfg.vocab_size), dtype=np.float32) if logits else None
+        temp = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, dtype=np.float64), (n,)))
+        tp = np.ascontiguousarray(np.broadcast_to(np.asarray(topp, dtype=np.float64), (n,)))
+        if rng is None:
+            if np.any(temp != 0.0):
+                raise ValueError("a sampled row needs an rng state")
+            st = None
+        else:
+            st = np.array([int(v) for v in rng], dtype=np.uint64)
+            if st.size != n:
+                raise ValueError("one rng state per row")
+        ptr = lambda a: None if a is None else a.ctypes.data
+        _check(lib().l2_step_batch(self._h, n, s.ctypes.data, nt.ctypes.data, tok.ctypes.data, p0.ctypes.data,
+                                   None if st is None else temp.ctypes.data, None if st is None else tp.ctypes.data, ptr(st),
+                                   picks.ctypes.data, ptr(out)))
+        after = None if st is None else [int(v) for v in st]
+        return (picks.tolist(), after, out) if logits else (picks.tolist(), after)
 
     @staticmethod
     def _rows(*cols):

@@ -1,0 +1,160 @@
+"""Continuous batching over the mixed step (runtime.Context.step_batch, include/llama2_hip.h: l2_step_batch).
+
+Every request runs exactly the reference's loop (llama2.ts:462-500): BOS (1) fed at position 0, then the prompt forced, then one pick
+per position (temperature 0: argmax; else one xorshift* draw from the request's own rng state), while pos < steps; a pick of BOS ends
+the request and is not fed.  The fed stream is [1, prompt..., picks...] at positions 0, 1, ..., so the first pick comes from the logits
+at position len(prompt).
+
+Each request holds one slot (a reserved sequence: sequences 0 .. slots-1) from admission to its end.  Each step is one step_batch call:
+one decode row per generating request, then prompt chunks of the oldest admitted requests that are still in their prompt, up to
+max_rows rows in all.  A chunk's rows are known tokens; when the chunk ends at the prompt's last position its pick is the request's
+first sampled token, otherwise it is fed with temperature 0 and its pick is thrown away (no draw).  Requests are admitted first come,
+first served; a finished request's slot goes to the next waiting one, which restarts the slot at position 0.  The scheduler is plain
+Python and deterministic for a given submission order; `ctx` is any object with step_batch (and get_option / cfg.seq_len, or pass
+slots / seq_len).
+"""
+import collections
+
+from . import runtime
+
+BOS = 1
+
+
+class Result:
+    """A finished request: tokens_fed (every token fed to the transformer, in order), finish ("bos" or "steps"), the rng state after its
+    last draw, and with keep_logits the logits each pick was made from (one row per pick, the BOS pick included)."""
+
+    __slots__ = ("tokens_fed", "finish", "rng_state", "logits")
+
+    def __init__(self, tokens_fed, finish, rng_state, logits=None):
+        self.tokens_fed, self.finish, self.rng_state, self.logits = tokens_fed, finish, rng_state, logits
+
+    def __repr__(self):
+        return "Result(tokens_fed=%d tokens, finish=%r, rng_state=%d)" % (len(self.tokens_fed), self.finish, self.rng_state)
+
+
+class _Request:
+    def __init__(self, rid, prompt, steps, temperature, topp, seed):
+        self.rid = rid
+        stop = prompt.index(BOS) if BOS in prompt else -1      # a forced BOS ends the reference's loop there (llama2.ts:497)
+        self.prompt = prompt if stop < 0 else prompt[:stop]
+        self.forced_bos = stop >= 0
+        self.known = [BOS] + self.prompt        # tokens of positions 0 .. len(prompt), known before any pick
+        self.steps, self.temperature, self.topp, self.rng = steps, float(temperature), float(topp), int(seed)
+        self.slot = None
+        self.fed = []                           # tokens fed so far; the next one goes to position len(fed)
+        self.next = None                        # the next token to feed once the prompt is done (a pick)
+        self.logits = []
+
+    @property
+    def in_prompt(self):
+        return len(self.fed) < len(self.known)
+
+
+class Scheduler:
+    def __init__(self, ctx, max_rows=64, keep_logits=False, slots=None, seq_len=None):
+        self.ctx = ctx
+        self.slots = int(slots) if slots is not None else int(ctx.get_option(runtime.OPT_SEQS))
+        self.seq_len = int(seq_len) if seq_len is not None else int(ctx.cfg.seq_len)
+        if self.slots < 1:
+            raise ValueError("no sequences reserved: call seq_reserve first")
+        if max_rows < self.slots:
+            raise ValueError("max_rows %d < %d slots: every generating request needs its decode row" % (max_rows, self.slots))
+        self.max_rows = int(max_rows)
+        self.keep_logits = bool(keep_logits)
+        self.waiting = collections.deque()
+        self.active = []                        # in admission order
+        self.free = list(range(self.slots))
+        self.results = {}
+        self._next_id = 0
+        self.calls = 0
+
+    def submit(self, prompt_ids, steps, temperature=0.0, topp=1.0, seed=1):
+        """Queue one request; returns its id.  steps <= seq_len (the reference's clamp is the caller's)."""
+        steps = int(steps)
+        if steps < 0 or steps > self.seq_len:
+            raise ValueError("steps %d outside [0, seq_len=%d]" % (steps, self.seq_len))
+        if temperature != temperature or topp != topp:
+            raise ValueError("temperature / topp is NaN")
+        rid = self._next_id
+        self._next_id += 1
+        self.waiting.append(_Request(rid, [int(t) for t in prompt_ids], steps, temperature, topp, seed))
+        return rid
+
+    @property
+    def idle(self):
+        return not self.waiting and not self.active
+
+    def _finish(self, r, how, done):
+        res = Result(r.fed, how, r.rng, r.logits if self.keep_logits else None)
+        self.results[r.rid] = done[r.rid] = res
+        if r.slot is not None:
+            self.active.remove(r)
+            self.free.append(r.slot)
+            self.free.sort()
+
+    def _admit(self, done):
+        while self.waiting and self.free:
+            r = self.waiting.popleft()
+            if r.steps == 0:                     # while (pos < steps) never runs
+                self._finish(r, "steps", done)
+                continue
+            r.slot = self.free.pop(0)
+            self.active.append(r)
+
+    def step(self):
+        """One step_batch call over the admitted requests; returns {rid: Result} of those that finished in it."""
+        done = {}
+        self._admit(done)
+        if not self.active:
+            return done
+        rows = []                                # (request, tokens, pos0, picks_count)
+        for r in self.active:
+            if not r.in_prompt:
+                rows.append((r, [r.next], len(r.fed), True))
+        budget = self.max_rows - len(rows)
+        for r in self.active:
+            if budget <= 0:
+                break
+            if r.in_prompt:
+                p = len(r.fed)
+                e = min(len(r.known), r.steps, p + budget)
+                # the chunk's last row is the prompt's last position: its pick is the request's first real one
+                rows.append((r, r.known[p:e], p, e == len(r.known) and not r.forced_bos))
+                budget -= e - p
+        seqs = [r.slot for r, _, _, _ in rows]
+        temp = [r.temperature if real else 0.0 for r, _, _, real in rows]
+        topp = [r.topp for r, _, _, _ in rows]
+        rng = [r.rng for r, _, _, _ in rows]
+        out = self.ctx.step_batch(seqs, [t for _, t, _, _ in rows], [p for _, _, p, _ in rows], temperature=temp, topp=topp, rng=rng,
+                                  logits=self.keep_logits)
+        self.calls += 1
+        picks, rng_after = out[0], out[1]
+        for i, (r, toks, p, real) in enumerate(rows):
+            r.fed.extend(toks)
+            if real:
+                if r.temperature != 0.0:
+                    r.rng = int(rng_after[i])
+                if self.keep_logits:
+                    r.logits.append(out[2][i])
+                nxt = int(picks[i])
+            elif r.in_prompt:
+                nxt = r.known[len(r.fed)]
+            elif r.forced_bos:
+                nxt = BOS
+            else:
+                nxt = None                       # stopped by steps inside the prompt
+            if nxt == BOS:
+                self._finish(r, "bos", done)
+            elif len(r.fed) >= r.steps:
+                self._finish(r, "steps", done)
+            else:
+                r.next = nxt
+        self._admit(done)
+        return done
+
+    def run(self):
+        """Step until every submitted request has finished; returns {rid: Result} of every request finished so far."""
+        while not self.idle:
+            self.step()
+        return dict(self.results)
