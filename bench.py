@@ -5,9 +5,9 @@ A "step" is ONE transformer() call (llama2.ts:205-303) = one decoded token, weig
 greedy feed (-t 0, llama2.ts:476-478) from BOS at pos 0, synthetic seeded weights of the named shape.
 `value` times the device-resident loop (forward + on-device argmax, no host round trip); the same
 steps through the blocking drop-in call l2_forward (logits handed to the host every token, as
-llama2.ts:468-478 consumes them) are reported next to it as `dropin_tok_s`.
+llama2.ts:468-478 consumes them) are reported next to it as `dropin_tok_s` by a --full run.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config llama2_7b|stories110M|stories15M] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config llama2_7b|stories110M|stories15M] [--dump-outputs DIR] [--full]
 
 K is the number of timed steps whatever the context window: a run longer than seq_len decodes the sequence again from BOS, in
 passes of seq_len steps (positions 0 .. seq_len-1, the remainder last).  --dump-outputs writes what the timed decode handed back in
@@ -16,20 +16,26 @@ its last step -- the logits of that step (float32) and the tokens its last pass 
 for output.  Both hold for N > 1 too (benchparts/worker.py): rank 0 writes the dump of the group's decode, the full logits
 after the all-gather.
 
-Everything in the JSON line is measured by this run:
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints the line
+(`value`, `ms_per_step`, the end-to-end HBM figures of those steps, how they were dispatched).  --full adds everything else, each
+figure measured by that run (the --no-* options drop legs of it):
+  * `parity`: the tokens of the timed run (and of the drop-in loop) against the real reference's golden tokens; exit code 3
+    on a mismatch;
+  * `dropin_tok_s`, `napi_dropin_tok_s`, `contract_tok_s`: the same steps through the blocking drop-in call (benchparts/dropin.py);
   * `roofline`: the dominant kernel (rmsnorm + w1/w3 GEMV + SwiGLU) timed in situ with HIP events on the
     library's stream; `traffic` = HBM bytes per launch from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE,
     gfx950 corrections of the MI355X guide) that this script runs over itself as child processes (--pmc-child)
-    BEFORE it touches the GPU; null when rocprofv3 is unavailable;
+    BEFORE it touches the GPU; null when rocprofv3 is unavailable; `per_kernel`: each GEMV phase back to back;
+  * the whole context window, its last 128 positions, the sampled loop, prompt ingestion, `tp_predicted`;
   * `cpu_baseline`: the C restatement of the reference (oracle/, one thread like the single-threaded reference)
-    timed on this box's host cores on a bounded sample of the same workload;
+    timed on the host cores of the GPU's machine on a bounded sample of the same workload;
   * `stories110M`: BASELINE.json's other named shape, same fields.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU, or by this script itself): Llama-2-7B is tensor-parallel (heads / FFN
 rows sharded, fp64 all-reduce of d partials twice per layer -- llama2.ts:270, 292) => strong scaling; shapes that do
 not shard run as independent replicas => weak scaling.  Every rank is a CPU-only SUPERVISOR that starts a fresh worker process per
 way of forming the group and bounds every phase of it (benchparts/ranks.py, benchparts/worker.py): a hang costs a deadline, not
-the line.
+the line.  --full does not change a multi-rank line.
 
 The legs live in benchparts/: profiler.py (rocprofv3 children), dropin.py (the drop-in boundary: ctypes, N-API), baselines.py (CPU),
 single.py (roofline, per-kernel, shard-step prediction), ranks.py + worker.py (N > 1).
@@ -58,10 +64,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=32)
     ap.add_argument("--config", default="llama2_7b", choices=sorted(configs.CONFIGS))
     ap.add_argument("--seed", type=int, default=configs.DEFAULT_SEED)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary measurements (stories110M block, long context, sampler, prefill)")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the l2_forward (host round trip per token) loop")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (roofline.traffic = null)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else (parity, drop-in loops, roofline, counters, per kernel, "
+                         "secondary measurements, CPU baseline); a plain run prints the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary measurements (stories110M block, long context, sampler, prefill)")
+    ap.add_argument("--no-dropin", action="store_true", help="with --full: skip the l2_forward (host round trip per token) loop")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 counter passes (roofline.traffic = null)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the timed decode's outputs (last step's logits, the tokens of its last pass) as DIR/<name>.npy")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
@@ -108,10 +117,10 @@ def main():
     passes = step_passes(K, S)
     device = int(os.environ.get("L2_BENCH_FORCE_DEVICE", os.environ.get("LOCAL_RANK", "0")))
 
-    # counter passes first: they are child processes, and nothing in THIS process has touched the GPU yet
+    # --full: counter passes first: they are child processes, and nothing in THIS process has touched the GPU yet
     traffic = {args.config: (None, "skipped (--no-pmc)")}
     trace_us, mfma = {}, {}
-    if not args.no_pmc:
+    if args.full and not args.no_pmc:
         traffic[args.config] = profiler.pmc_traffic(args.config, args.seed)
         trace_us[args.config] = profiler.kernel_trace_us(args.config, args.seed)
         mfma[args.config] = profiler.mfma_instructions(args.config, args.seed)
@@ -166,7 +175,8 @@ def main():
                        args.config, K, Kseq, "" if len(passes) == 1 else ", %d passes of at most seq_len = %d steps" % (len(passes), S)),
                    "header": list(hdr), "parallelism": "single",
                    "loop": ("device-resident (forward + argmax on GPU, %s) -- `value` times THIS loop, a SURVEY.md 8(f1) extra; the contract's own call "
-                            "(one blocking transformer() per token, logits to the host) is `contract_tok_s`" % dispatch_note(ctx)),
+                            "(one blocking transformer() per token, logits to the host) is `contract_tok_s`%s"
+                            % (dispatch_note(ctx), "" if args.full else " of a --full run")),
                    "weights": "fp32, ONE copy on the device (%d MiB): the matrices of the streaming phases repacked in the order the chip consumes them "
                               "(%d MiB, DESIGN.md section 3), everything else row-major as the checkpoint stores it"
                               % (ctx.get_option(runtime.OPT_WEIGHT_MIB), ctx.get_option(runtime.OPT_PACKED_MIB)),
@@ -177,11 +187,15 @@ def main():
         "hbm_gbs_end_to_end": round(bpt * value / 1e9, 2),
         "hbm_frac_end_to_end": round(bpt * value / 1e9 / HBM_PEAK_GBS, 4),
     }
+    if under_profiler() and os.environ.get("L2_USE_GRAPH") == "0":
+        out["profiled"] = "this run was started under a profiler: eager launches instead of a recorded step per token (host-bound; read the kernel durations, not `value`)"
+    if not args.full:
+        ctx.close()
+        print(json.dumps(out))
+        return
 
     # the tokens of the TIMED run against the real reference's tokens for this checkpoint (fixtures are data: they travel)
     out["parity"] = passes_parity(args.config, args.seed, pass_tokens)
-    if under_profiler() and os.environ.get("L2_USE_GRAPH") == "0":
-        out["profiled"] = "this run was started under a profiler: eager launches instead of a recorded step per token (host-bound; read the kernel durations, not `value`)"
     if not args.no_dropin:   # the Kseq steps of the longest pass through the blocking drop-in boundary (logits to the host every token)
         rate, dropin_tokens = dropin_loop(ctx, Kseq)
         out["dropin_tok_s"] = round(rate, 3)

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "stories15M", "--steps", "32", "--warmup", "4"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "stories15M", "--steps", "32", "--warmup", "4", "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
@@ -62,7 +62,7 @@ def test_bench_exits_nonzero_when_the_timed_tokens_are_not_the_references(tmp_pa
     g["seed"] = g["seed"] + 1
     json.dump(g, open(work / "tests" / "golden" / "stories15M.json", "w"))
     r = subprocess.run([sys.executable, str(work / "bench.py"), "--config", "stories15M", "--steps", "16", "--warmup", "2", "--seed", str(g["seed"]),
-                        "--no-cpu-baseline", "--no-pmc", "--no-extra", "--no-dropin"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        "--full", "--no-cpu-baseline", "--no-pmc", "--no-extra", "--no-dropin"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 3, (r.returncode, r.stderr.decode()[-1500:])
     j = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][0])
     assert j["parity"]["equal_to_reference_golden"] is False and "first_mismatch" in j["parity"]
@@ -103,7 +103,7 @@ def test_bench_steps_past_seq_len_and_dump(tmp_path):
     """--steps sets the number of timed steps even above seq_len (stories15M: 256): 300 steps are a pass of 256 and one of 44, each
     from BOS, both checked against the reference's tokens; --dump-outputs writes what the last step handed back."""
     d = tmp_path / "dump"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "stories15M", "--steps", "300", "--warmup", "2", "--no-extra",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "stories15M", "--steps", "300", "--warmup", "2", "--full", "--no-extra",
                         "--no-pmc", "--no-dropin", "--no-cpu-baseline", "--dump-outputs", str(d)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     j = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][0])
@@ -236,6 +236,26 @@ def test_bench_gpus_one_stays_in_process():
     j = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][0])
     assert j["n_gpus"] == 1 and j["config"]["parallelism"] == "single" and "tp" not in j
     assert j["config"]["weights_mib"]["repacked"] == 0
+
+
+def test_plain_run_prints_the_headline_only():
+    """Without --full the run sets up, warms up, times its steps and prints the headline: none of the legs behind --full, and little
+    time spent outside the steps."""
+    import time
+    t0 = time.monotonic()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "stories15M", "--steps", "64", "--warmup", "4"],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    took = time.monotonic() - t0
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "hbm_frac_end_to_end"):
+        assert k in j, k
+    assert j["steps"] == 64 and j["warmup"] == 4 and abs(j["value"] - 1e3 / j["ms_per_step"]) / j["value"] < 0.01
+    for k in ("parity", "roofline", "per_kernel", "cpu_baseline", "dropin_tok_s", "contract_tok_s", "whole_context_tok_s", "prefill_tok_s", "stories110M"):
+        assert k not in j, k
+    assert took - (64 + 4) * j["ms_per_step"] * 1e-3 < 30, took
 
 
 @pytest.mark.skipif(os.environ.get("L2_TEST_WIDE_PROCESS_GROUPS", "0") != "1",

@@ -5,12 +5,12 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/r06prof
 rm -rf $out; mkdir -p $out
 timeout 2400 python -m pytest tests -m gpu -q --durations=25 2>&1 | tail -40 > $out/pytest_gpu.txt
-# bench lines (default = what the driver runs; parity of the timed tokens against the reference goldens, roofline.traffic from the PMC
-# passes inside the run, kernel_trace_us from a rocprofv3 --kernel-trace child, cpu_baseline on this box, tp_predicted from shard-timing contexts)
-python bench.py > $out/bench_default_llama2_7b.json 2> $out/bench_default.err
-L2_BENCH_SKIP_JS_7B=1 python bench.py --steps 20 --warmup 5 > $out/bench_driver_style_llama2_7b.json 2>/dev/null      # (the in-process JS baseline of the 7B shape: once is enough)
-python bench.py --config stories110M > $out/stories110M_bench.json 2>/dev/null
-python bench.py --config stories15M > $out/stories15M_bench.json 2>/dev/null
+# bench lines with --full (parity of the timed tokens against the reference goldens, roofline.traffic from the PMC passes inside the run,
+# kernel_trace_us from a rocprofv3 --kernel-trace child, cpu_baseline on the GPU's host, tp_predicted from shard-timing contexts)
+python bench.py --full > $out/bench_default_llama2_7b.json 2> $out/bench_default.err
+L2_BENCH_SKIP_JS_7B=1 python bench.py --full --steps 20 --warmup 5 > $out/bench_driver_style_llama2_7b.json 2>/dev/null      # (the in-process JS baseline of the 7B shape: once is enough)
+python bench.py --full --config stories110M > $out/stories110M_bench.json 2>/dev/null
+python bench.py --full --config stories15M > $out/stories15M_bench.json 2>/dev/null
 # what `python bench.py --gpus N` prints when all ranks land on this one GPU (supervised stages; the ranks end up meeting through files)
 L2_BENCH_FORCE_DEVICE=0 python bench.py --gpus 2 --config llama2_7b_L2 --steps 64 --warmup 8 --no-cpu-baseline > $out/bench_gpus2_two_ranks_one_gpu.json 2> $out/bench_gpus2.err
 L2_BENCH_FORCE_DEVICE=0 L2_TP_WAIT_S=20 python bench.py --gpus 8 --config llama2_7b_L2 --steps 64 --warmup 8 --no-cpu-baseline > $out/bench_gpus8_eight_ranks_one_gpu.json 2> $out/bench_gpus8.err
