@@ -28,7 +28,8 @@ extern "C" {
  * The batched decode of independent sequences (l2_seq_reserve .. l2_read_seq_cache, option key L2_OPT_SEQS) joined the surface without a
  * version step: it only adds, and a binding detects it by the presence of the l2_seq_reserve symbol.  So did its sampled loop
  * (l2_decode_sample_batch, option keys L2_OPT_BATCH_SAMPLED_TOKENS / _SERIAL), detected by its own symbol, and so were the packed
- * prompts (l2_seq_prefill_batch) and the mixed step (l2_step_batch). */
+ * prompts (l2_seq_prefill_batch) and the mixed step (l2_step_batch), and so are the per-token log-probabilities (l2_seq_score_batch,
+ * l2_step_batch_logprobs). */
 #define L2_ABI_VERSION 5
 
 enum {
@@ -264,6 +265,28 @@ int l2_decode_sample_batch(l2_ctx* ctx, int n, const int32_t* seqs, const int32_
  * context's own cache; the single-sequence state is left alone. */
 int l2_step_batch(l2_ctx* ctx, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
                   const double* temperature, const double* topp, uint64_t* rng_state, int32_t* picks_out, float* logits_out);
+/* Teacher-forced scoring of n sequences.  Feeds exactly as l2_seq_prefill_batch does (same packing, same launch sequences: every
+ * cache and every sequence's next position ends bit for bit as that call leaves it).  For every fed row r (R = sum n_tokens rows,
+ * in call order) it writes lp_out[r] = log-softmax of that position's logits at targets[r] (fp64; targets[r] == -1: NaN),
+ * argmax_out[r] (may be NULL) = the first maximum (llama2.ts:364-366), and for top_k > 0 the top_k largest logits' ids / lps
+ * at top_ids_out[r * top_k ..] / top_lp_out[r * top_k ..] (descending; equal logits by ascending id; entry 0 = argmax_out[r]).
+ * Each row's logits come from the last-row classifier's arithmetic (fp64 MFMA, one fp32 rounding per logit); then, in fp64,
+ * lse = m + log(sum_j exp(x_j - m)) with m = max_j x_j and lp = x_t - lse.  A row holding a NaN or +inf logit, or none above -inf,
+ * has NaN for every lp (its argmax and top ids still follow the first-maximum rules); a -inf logit of any other row has lp -inf.
+ * Argument rules of l2_seq_prefill_batch, plus L2_E_ARG for a null targets or lp_out, a target outside [-1, vocab_size), top_k
+ * outside [0, 20] or above vocab_size, and top_k > 0 with a null top array.  A refused call writes nothing.  L2_OPT_CHECK_POS,
+ * L2_OPT_EXACT_ATTENTION and L2_OPT_PREFILL_F32_MFMA apply as they do to l2_seq_prefill_batch.  Sequence 0 is the context's own
+ * cache; the single-sequence state is left alone.  Blocking. */
+int l2_seq_score_batch(l2_ctx* ctx, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
+                       const int32_t* targets, int top_k, double* lp_out, int32_t* argmax_out, int32_t* top_ids_out, double* top_lp_out);
+/* l2_step_batch, unchanged in every output (picks, rng states, logits, caches: bit for bit), plus for each row i:
+ * pick_lp_out[i] = the log-probability of picks_out[i] under the UNSCALED logits (the model's distribution, temperature and top-p
+ * not applied) and, for top_k > 0, that row's top_k ids / lps at top_ids_out[i * top_k ..] / top_lp_out[i * top_k ..], by the rules
+ * of l2_seq_score_batch.  Argument rules of l2_step_batch, plus L2_E_ARG for a null pick_lp_out, top_k outside [0, 20] or above
+ * vocab_size, and top_k > 0 with a null top array.  Sampled tokens count into L2_OPT_BATCH_SAMPLED_TOKENS / _SERIAL. */
+int l2_step_batch_logprobs(l2_ctx* ctx, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
+                           const double* temperature, const double* topp, uint64_t* rng_state, int32_t* picks_out, float* logits_out,
+                           int top_k, double* pick_lp_out, int32_t* top_ids_out, double* top_lp_out);
 /* Read sequence `seq`'s key / value cache (which = L2_S_KEY_CACHE / L2_S_VALUE_CACHE; layer -1 = all), like l2_read_state. */
 int l2_read_seq_cache(l2_ctx* ctx, int seq, int which, int layer, float* out, size_t n_floats);
 

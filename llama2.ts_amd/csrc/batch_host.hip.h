@@ -1,5 +1,5 @@
 // batch_host.hip.h -- host side of batched decode (batch.hip.h): l2_seq_reserve, l2_seq_prefill, l2_seq_prefill_batch, l2_forward_batch,
-// l2_decode_greedy_batch, l2_decode_sample_batch, l2_step_batch, l2_read_seq_cache.
+// l2_decode_greedy_batch, l2_decode_sample_batch, l2_step_batch, l2_seq_score_batch, l2_step_batch_logprobs, l2_read_seq_cache.
 // Part of the one translation unit llama2_hip.hip (included there, in order); not a stand-alone header.
 #pragma once
 
@@ -28,6 +28,10 @@ struct BatchState {
   float *px = nullptr, *pxn = nullptr, *pq = nullptr, *pxb = nullptr, *phb = nullptr;   // [BP_ROWS][d | max(d, h) | d | d | h]
   int* ptab = nullptr;                    // device: bp_tables' layout, ptab_cap ints
   size_t ptab_cap = 0;
+  // Log-probabilities (logprob.hip.h), allocated at the first call that asks for them
+  float* slogits = nullptr;               // [BP_ROWS][V]: the logits of every row of one packed launch sequence (l2_seq_score_batch)
+  char* lpbuf = nullptr;                  // device: a call's targets and outputs (lp_bufs' layout), lpbuf_cap bytes
+  size_t lpbuf_cap = 0;
   int* seq_of() const { return tab; }
   int* tok_of() const { return tab + BT_MAX; }
   int* pos_of() const { return tab + 2 * BT_MAX; }
@@ -44,7 +48,8 @@ static void batch_free(l2_ctx* c) {
   if (!b) return;
   bt_drop_graphs(b);
   for (size_t s = 1; s < b->kc.size(); ++s) { if (b->kc[s]) hipFree(b->kc[s]); if (b->vc[s]) hipFree(b->vc[s]); }
-  void* dev[] = {b->d_kc, b->d_vc, b->tab, b->out, b->x, b->xn, b->q, b->xb, b->hb, b->logits, b->px, b->pxn, b->pq, b->pxb, b->phb, b->ptab};
+  void* dev[] = {b->d_kc, b->d_vc, b->tab, b->out, b->x, b->xn, b->q, b->xb, b->hb, b->logits, b->px, b->pxn, b->pq, b->pxb, b->phb, b->ptab,
+                 b->slogits, b->lpbuf};
   for (void* p : dev) if (p) hipFree(p);
   if (b->h_tab) hipHostFree(b->h_tab);
   if (b->smp) { l2s::destroy_rows(b->smp); delete b->smp; }
@@ -438,13 +443,57 @@ static int bp_check(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_toke
   return L2_OK;
 }
 
+// The device side of a call's log-probabilities (lp_bufs): per row its target, lp and argmax; per row and rank its top-k id and lp.
+struct LpDev { int* target; double* lp; int* amax; int* top_ids; double* top_lp; };
+
+// lp_rows_kernel over `rows` rows of `logits` (targets `target`), its outputs at row r0 of `o`: the one-key instance when no top-k is
+// asked for (round 0 is the argmax), else the LP_TOPK_MAX-key one.
+static hipError_t launch_lp_rows(const l2_ctx* c, const float* logits, int rows, const int* target, const LpDev& o, size_t r0, int k, hipStream_t st) {
+  const LpRowsArgs a = {logits, target, o.lp + r0, o.amax + r0, o.top_ids + r0 * k, o.top_lp + r0 * k, c->V, k};
+  if (k == 0) hipLaunchKernelGGL(lp_rows_kernel<1>, dim3(rows), dim3(1024), 0, st, a);
+  else hipLaunchKernelGGL(lp_rows_kernel<LP_TOPK_MAX>, dim3(rows), dim3(1024), 0, st, a);
+  return hipGetLastError();
+}
+
+// The device buffers of a call over `rows` rows with top-k `k` (grown when too small): [rows] lp, [rows][k] top lps (doubles first),
+// then [rows] targets, [rows] argmax, [rows][k] top ids.
+static int lp_bufs(l2_ctx* c, size_t rows, int k, LpDev& o) {
+  BatchState* b = c->bt;
+  const size_t need = rows * (sizeof(double) * (1 + k) + sizeof(int) * (2 + k));
+  if (need > b->lpbuf_cap) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (b->lpbuf) { HIPCHK(hipFree(b->lpbuf)); b->lpbuf = nullptr; b->lpbuf_cap = 0; }
+    HIPCHK(hipMalloc(&b->lpbuf, need));
+    b->lpbuf_cap = need;
+  }
+  o.lp = reinterpret_cast<double*>(b->lpbuf);
+  o.top_lp = o.lp + rows;
+  o.target = reinterpret_cast<int*>(o.top_lp + rows * k);
+  o.amax = o.target + rows;
+  o.top_ids = o.amax + rows;
+  return L2_OK;
+}
+
+// Bytes from the start of b->lpbuf to p (a column of an LpDev that lp_bufs carved out of it).
+static size_t lp_span(const BatchState* b, const void* p) { return (size_t)((const char*)p - b->lpbuf); }
+
+// Arguments of the log-probability calls that need no context: top_k in [0, LP_TOPK_MAX], its arrays given when top_k > 0.
+static int lp_check_k(int top_k, const void* top_ids_out, const void* top_lp_out) {
+  if (top_k < 0 || top_k > LP_TOPK_MAX) return fail(L2_E_ARG, "top_k %d outside [0, %d]", top_k, (int)LP_TOPK_MAX);
+  if (top_k > 0 && (!top_ids_out || !top_lp_out)) return fail(L2_E_ARG, "top_k %d with a null top_ids_out / top_lp_out", top_k);
+  return L2_OK;
+}
+
 // Enqueue the launch sequences of n checked runs given in packing order (R rows in all).  The first nd runs are decode rows (one row
 // each, l2_step_batch; 0 for l2_seq_prefill_batch): they lie in the first launch sequence, are cut into no tile, and take the decode
 // attention form per (head, row) -- bt_attn_tile_kernel, at any head size and position -- while the tiles of the longer runs take
 // bp_attn_mfma_kernel with its LDS sized by the longest of them.  `logits`: gather every run's last row, final norm and classifier ->
-// b->logits rows 0 .. n-1.  htab holds the uploaded tables: the caller keeps it until the stream has been synchronised.
+// b->logits rows 0 .. n-1.  htab holds the uploaded tables: the caller keeps it until the stream has been synchronised.  `score`
+// (l2_seq_score_batch): after each launch sequence's layers, the final norm and the classifier of EVERY row of it (pf_gemm_kernel
+// <MODE_CLS_ROWS> in 64-row slices: the last-row classifier's arithmetic) into b->slogits, then lp_rows_kernel over them with the
+// targets and outputs of `score` at the launch sequence's first row -- all before the next launch sequence overwrites the rows.
 static int bp_enqueue(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0, size_t R, int nd,
-                      bool logits, std::vector<int>& htab) {
+                      bool logits, std::vector<int>& htab, const LpDev* score = nullptr, int top_k = 0) {
   BatchState* b = c->bt;
   hipStream_t st = c->stream;
   const size_t d = c->d, h = c->h;
@@ -564,6 +613,19 @@ static int bp_enqueue(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_to
       launch_pf_gemm<MODE_W2>(c, a, 4, tt, chunks, st);
       LCHK(hipGetLastError());
     }
+    if (score) {      // every row of this launch sequence: final rmsnorm, classifier (llama2.ts:299-302), log-probabilities
+      hipLaunchKernelGGL(pf_norm_kernel, dim3(nt), dim3(256), 0, st, b->pxn, (const float*)b->px, c->w[L2_T_RMS_FINAL], c->d);
+      for (int s0 = 0; s0 < m; s0 += PF_T) {
+        const int ms = std::min(m - s0, (int)PF_T);
+        PfArgs a;
+        memset(&a, 0, sizeof(a));
+        bt_cls_weights(c, a);
+        a.xin = b->pxn + (size_t)s0 * d; a.out = b->slogits + (size_t)s0 * c->V; a.n = c->d; a.rows = c->V; a.dim = c->d; a.nvalid = ms;
+        bt_gemm<MODE_CLS_ROWS>(c, a, (ms > 32) ? 4 : (ms > 16) ? 2 : 1, st);
+      }
+      LCHK(hipGetLastError());
+      LCHK(launch_lp_rows(c, b->slogits, m, score->target + r0, *score, (size_t)r0, top_k, st));
+    }
     // the residual rows of the runs that end here, into b->x rows seq_a .. seq_b - 1 (pf_embed_kernel as a row gather)
     if (logits && seq_b[k] > seq_a[k]) {
       hipLaunchKernelGGL(pf_embed_kernel, dim3(seq_b[k] - seq_a[k]), dim3(256), 0, st, b->x + (size_t)seq_a[k] * d, (const float*)b->px, dgsrc + seq_a[k],
@@ -608,13 +670,53 @@ extern "C" int l2_seq_prefill_batch(l2_ctx* c, int n, const int32_t* seqs, const
   return L2_OK;
 }
 
-// ---- the mixed step (l2_step_batch) --------------------------------------------------------------
+// ---- teacher-forced scoring (l2_seq_score_batch) --------------------------------------------------
+// l2_seq_prefill_batch's launch sequences (same packing, no last-row gather), with every row's logits and log-probabilities made inside
+// them (bp_enqueue's `score`); only the per-row results come back.
+extern "C" int l2_seq_score_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
+                                  const int32_t* targets, int top_k, double* lp_out, int32_t* argmax_out, int32_t* top_ids_out, double* top_lp_out) {
+  if (!targets || !lp_out) return fail(L2_E_ARG, "null targets / lp_out");
+  int rc = lp_check_k(top_k, top_ids_out, top_lp_out);
+  if (rc) return rc;
+  size_t R = 0;
+  rc = bp_check(c, n, seqs, n_tokens, tokens, pos0, &R);
+  if (rc) return rc;
+  for (size_t r = 0; r < R; ++r)
+    if (targets[r] < -1 || targets[r] >= c->V) return fail(L2_E_ARG, "target %d (packed row %zu) outside [-1, vocab_size=%d)", targets[r], r, c->V);
+  if (top_k > c->V) return fail(L2_E_ARG, "top_k %d > vocab_size %d", top_k, c->V);
+  rc = ensure_ready(c);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  BatchState* b = c->bt;
+  hipStream_t st = c->stream;
+  if (!b->slogits) HIPCHK(hipMalloc(&b->slogits, (size_t)BP_ROWS * c->V * sizeof(float)));
+  LpDev o;
+  rc = lp_bufs(c, R, top_k, o);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(o.target, targets, R * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  std::vector<int> htab;
+  rc = bp_enqueue(c, n, seqs, n_tokens, tokens, pos0, R, 0, false, htab, &o, top_k);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(lp_out, o.lp, R * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (argmax_out) HIPCHK(hipMemcpyAsync(argmax_out, o.amax, R * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (top_k > 0) {
+    HIPCHK(hipMemcpyAsync(top_ids_out, o.top_ids, R * top_k * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(top_lp_out, o.top_lp, R * top_k * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  bp_set_next(c, n, seqs, n_tokens, pos0);
+  return L2_OK;
+}
+
+// ---- the mixed step (l2_step_batch, l2_step_batch_logprobs) ---------------------------------------
 // The runs are reordered so that the one-row runs (decode rows) come first, then packed and run as above; every run's last-position
 // logits then get one pick on the device: bt_argmax_kernel when no row samples, else the row sampler's phases and bt_pick_kernel.  The
 // picks land in the batch step's token table (its position and start columns zeroed first, so each row's pick is also out[r][0]); only
-// they, the rng states and the optional logits come back.
-extern "C" int l2_step_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
-                             const double* temperature, const double* topp, uint64_t* rng_state, int32_t* picks_out, float* logits_out) {
+// they, the rng states and the optional logits come back.  With pick_lp_out (l2_step_batch_logprobs), lp_rows_kernel then reads the
+// picks from that table as its targets and the unscaled logits rows; without it the step enqueues nothing more.
+static int bt_step(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
+                   const double* temperature, const double* topp, uint64_t* rng_state, int32_t* picks_out, float* logits_out,
+                   int top_k, double* pick_lp_out, int32_t* top_ids_out, double* top_lp_out) {
   size_t R = 0;
   int rc = bp_check(c, n, seqs, n_tokens, tokens, pos0, &R);
   if (rc) return rc;
@@ -627,6 +729,7 @@ extern "C" int l2_step_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_
     if (temperature[i] != 0.0) any = true;
   }
   if (any && c->V > l2s::MAX_VOCAB) return fail(L2_E_CONFIG, "device sampler supports vocabularies up to %d", (int)l2s::MAX_VOCAB);
+  if (top_k > c->V) return fail(L2_E_ARG, "top_k %d > vocab_size %d", top_k, c->V);
 
   // packing order: decode rows (runs of one row) first, then the longer runs, each group in call order
   std::vector<int> ord;
@@ -655,6 +758,11 @@ extern "C" int l2_step_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_
     rc = bt_ensure_sampler(c, "l2_step_batch");
     if (rc) return rc;
   }
+  LpDev o = {};
+  if (pick_lp_out) {
+    rc = lp_bufs(c, (size_t)n, top_k, o);
+    if (rc) return rc;
+  }
   HIPCHK(hipStreamSynchronize(st));      // (the pinned tables: the previous call's copies have completed)
   std::vector<int> htab;
   rc = bp_enqueue(c, n, ps.data(), pn.data(), ptok.data(), pp.data(), R, nd, true, htab);
@@ -674,6 +782,12 @@ extern "C" int l2_step_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_
                        b->out, c->S);
   }
   LCHK(hipGetLastError());
+  std::vector<char> lpbytes;
+  if (pick_lp_out) {      // after the pick: its log-probability under the unscaled logits, and the top-k
+    LCHK(launch_lp_rows(c, b->logits, n, b->tok_of(), o, 0, top_k, st));
+    lpbytes.resize(lp_span(b, o.top_ids + (size_t)n * top_k));      // one copy of lp_bufs' layout, up to its last column
+    HIPCHK(hipMemcpyAsync(lpbytes.data(), b->lpbuf, lpbytes.size(), hipMemcpyDeviceToHost, st));
+  }
   std::vector<int32_t> picks(n);
   HIPCHK(hipMemcpyAsync(picks.data(), b->tok_of(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   std::vector<float> lg;
@@ -691,6 +805,13 @@ extern "C" int l2_step_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_
     const int i = ord[j];
     picks_out[i] = picks[j];
     if (!lg.empty()) memcpy(logits_out + (size_t)i * c->V, lg.data() + (size_t)j * c->V, (size_t)c->V * sizeof(float));
+    if (pick_lp_out) {      // the columns of `o`, at their offsets in the host copy
+      const double* plp = reinterpret_cast<const double*>(lpbytes.data() + lp_span(b, o.lp));
+      const double* tlp = reinterpret_cast<const double*>(lpbytes.data() + lp_span(b, o.top_lp));
+      const int32_t* tid = reinterpret_cast<const int32_t*>(lpbytes.data() + lp_span(b, o.top_ids));
+      pick_lp_out[i] = plp[j];
+      for (int q = 0; q < top_k; ++q) { top_ids_out[(size_t)i * top_k + q] = tid[(size_t)j * top_k + q]; top_lp_out[(size_t)i * top_k + q] = tlp[(size_t)j * top_k + q]; }
+    }
     if (any) {
       rng_state[i] = b->smp->h_rng[j];
       for (int k = 0; k < 2; ++k) { const unsigned long long v = b->smp_stats[k] + b->smp->h_stats[2 * j + k]; b->smp_stats[k] = v < b->smp_stats[k] ? ~0ull : v; }
@@ -698,6 +819,20 @@ extern "C" int l2_step_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_
   }
   bp_set_next(c, n, seqs, n_tokens, pos0);
   return L2_OK;
+}
+
+extern "C" int l2_step_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
+                             const double* temperature, const double* topp, uint64_t* rng_state, int32_t* picks_out, float* logits_out) {
+  return bt_step(c, n, seqs, n_tokens, tokens, pos0, temperature, topp, rng_state, picks_out, logits_out, 0, nullptr, nullptr, nullptr);
+}
+
+extern "C" int l2_step_batch_logprobs(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
+                                      const double* temperature, const double* topp, uint64_t* rng_state, int32_t* picks_out, float* logits_out,
+                                      int top_k, double* pick_lp_out, int32_t* top_ids_out, double* top_lp_out) {
+  if (!pick_lp_out) return fail(L2_E_ARG, "null pick_lp_out");
+  const int rc = lp_check_k(top_k, top_ids_out, top_lp_out);
+  if (rc) return rc;
+  return bt_step(c, n, seqs, n_tokens, tokens, pos0, temperature, topp, rng_state, picks_out, logits_out, top_k, pick_lp_out, top_ids_out, top_lp_out);
 }
 
 extern "C" int l2_read_seq_cache(l2_ctx* c, int seq, int which, int layer, float* out, size_t n_floats) {

@@ -37,7 +37,7 @@ ABI_SYMBOLS = ["l2_abi_version", "l2_device_count", "l2_last_error", "l2_create"
                "l2_decode_greedy", "l2_decode_sample", "l2_debug_running_sums", "l2_read_state", "l2_set_option", "l2_get_option", "l2_timer_start",
                "l2_timer_stop", "l2_bench_gemv", "l2_bench_decode", "l2_load_checkpoint", "l2_get_header", "l2_prefill", "l2_bench_dominant_in_situ", "l2_tp_mode", "l2_create_ex", "l2_bench_tokens", "l2_dispatch_reason",
                "l2_seq_reserve", "l2_seq_prefill", "l2_forward_batch", "l2_decode_greedy_batch", "l2_read_seq_cache",
-               "l2_decode_sample_batch", "l2_seq_prefill_batch", "l2_step_batch"]
+               "l2_decode_sample_batch", "l2_seq_prefill_batch", "l2_step_batch", "l2_seq_score_batch", "l2_step_batch_logprobs"]
 
 
 class L2Error(RuntimeError):
@@ -100,6 +100,8 @@ def lib():
     L.l2_decode_sample_batch.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]
     L.l2_seq_prefill_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.l2_step_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.l2_seq_score_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.l2_step_batch_logprobs.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     for name in ABI_SYMBOLS:   # fail at load time, not at first use, if the .so is stale
         getattr(L, name)
     _lib = L
@@ -267,11 +269,40 @@ class Context:
                                           out.ctypes.data))
         return out
 
-    def step_batch(self, seqs, runs, pos0, temperature=0.0, topp=1.0, rng=None, logits=False):
+    def seq_score_batch(self, seqs, runs, pos0=0, targets=None, top_k=0):
+        """Teacher-forced scoring: feed runs[i] into sequence seqs[i] at pos0[i].. exactly as seq_prefill_batch does, and return for
+        every fed row, in packed order (the runs back to back): (lp, argmax, top_ids, top_lp) -- the fp64 log-probability of the row's
+        target under that position's logits (NaN for a target of -1), the first maximum, and the top_k largest logits' ids / lps
+        ((R, top_k) arrays).  targets: R ints in [-1, V), by default each row's next token of its run and -1 at the run's end."""
+        s = np.ascontiguousarray(seqs, dtype=np.int32).reshape(-1)
+        rs = [np.ascontiguousarray(r, dtype=np.int32).reshape(-1) for r in runs]
+        if len(rs) != s.size:
+            raise ValueError("one run per sequence")
+        p0 = np.ascontiguousarray(np.broadcast_to(np.asarray(pos0, dtype=np.int32), (s.size,)))
+        nt = np.array([r.size for r in rs], dtype=np.int32)
+        tok = np.ascontiguousarray(np.concatenate(rs) if rs else np.zeros(0, dtype=np.int32), dtype=np.int32)
+        if targets is None:
+            tg = np.concatenate([np.append(r[1:], -1) for r in rs]).astype(np.int32) if rs else np.zeros(0, dtype=np.int32)
+        else:
+            tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+            if tg.size != tok.size:
+                raise ValueError("one target per fed row")
+        R, k = tok.size, int(top_k)
+        lp = np.empty(R, dtype=np.float64)
+        am = np.empty(R, dtype=np.int32)
+        ids = np.empty((R, max(k, 0)), dtype=np.int32)
+        tlp = np.empty((R, max(k, 0)), dtype=np.float64)
+        _check(lib().l2_seq_score_batch(self._h, s.size, s.ctypes.data, nt.ctypes.data, tok.ctypes.data, p0.ctypes.data, tg.ctypes.data, k,
+                                        lp.ctypes.data, am.ctypes.data, ids.ctypes.data if k > 0 else None,
+                                        tlp.ctypes.data if k > 0 else None))
+        return lp, am, ids, tlp
+
+    def step_batch(self, seqs, runs, pos0, temperature=0.0, topp=1.0, rng=None, logits=False, logprobs=None):
         """One mixed step: feed runs[i] into sequence seqs[i] at pos0[i].. (a run of one token is a decode row), then one pick per row
         from its run's last-position logits, made on the device (temperature 0: argmax, no draw; else one xorshift* draw from rng[i]).
         temperature / topp: a scalar or one per row; rng: one state per row (uint64), or None when every row is greedy.  Returns
-        (picks, rng_after[, (n, V) logits the picks were made from])."""
+        (picks, rng_after[, (n, V) logits the picks were made from]).  logprobs = k (0 .. 20) also returns (pick_lp, top_ids, top_lp):
+        each pick's fp64 log-probability under the unscaled logits, and the k largest logits' ids / lps per row ((n, k) arrays)."""
         s = np.ascontiguousarray(seqs, dtype=np.int32).reshape(-1)
         n = s.size
         rs = [np.ascontiguousarray(r, dtype=np.int32).reshape(-1) for r in runs]
@@ -293,11 +324,22 @@ class Context:
             if st.size != n:
                 raise ValueError("one rng state per row")
         ptr = lambda a: None if a is None else a.ctypes.data
-        _check(lib().l2_step_batch(self._h, n, s.ctypes.data, nt.ctypes.data, tok.ctypes.data, p0.ctypes.data,
-                                   None if st is None else temp.ctypes.data, None if st is None else tp.ctypes.data, ptr(st),
-                                   picks.ctypes.data, ptr(out)))
+        if logprobs is None:
+            _check(lib().l2_step_batch(self._h, n, s.ctypes.data, nt.ctypes.data, tok.ctypes.data, p0.ctypes.data,
+                                       None if st is None else temp.ctypes.data, None if st is None else tp.ctypes.data, ptr(st),
+                                       picks.ctypes.data, ptr(out)))
+            after = None if st is None else [int(v) for v in st]
+            return (picks.tolist(), after, out) if logits else (picks.tolist(), after)
+        k = int(logprobs)
+        plp = np.empty(n, dtype=np.float64)
+        ids = np.empty((n, max(k, 0)), dtype=np.int32)
+        tlp = np.empty((n, max(k, 0)), dtype=np.float64)
+        _check(lib().l2_step_batch_logprobs(self._h, n, s.ctypes.data, nt.ctypes.data, tok.ctypes.data, p0.ctypes.data,
+                                            None if st is None else temp.ctypes.data, None if st is None else tp.ctypes.data, ptr(st),
+                                            picks.ctypes.data, ptr(out), k, plp.ctypes.data, ids.ctypes.data if k > 0 else None,
+                                            tlp.ctypes.data if k > 0 else None))
         after = None if st is None else [int(v) for v in st]
-        return (picks.tolist(), after, out) if logits else (picks.tolist(), after)
+        return (picks.tolist(), after) + ((out,) if logits else ()) + ((plp, ids, tlp),)
 
     @staticmethod
     def _rows(*cols):

@@ -12,6 +12,10 @@ first sampled token, otherwise it is fed with temperature 0 and its pick is thro
 first served; a finished request's slot goes to the next waiting one, which restarts the slot at position 0.  The scheduler is plain
 Python and deterministic for a given submission order; `ctx` is any object with step_batch (and get_option / cfg.seq_len, or pass
 slots / seq_len).
+
+A request submitted with logprobs=k (0 .. 20) gets, for each of its picks (the BOS pick included), the pick's log-probability under the
+model's unscaled logits and the k most likely tokens with theirs, in Result.logprobs.  Only a step that holds such a request calls the
+logprobs form of the step (l2_step_batch_logprobs), which leaves picks, rng states and caches exactly as the plain step does.
 """
 import collections
 
@@ -22,19 +26,21 @@ BOS = 1
 
 class Result:
     """A finished request: tokens_fed (every token fed to the transformer, in order), finish ("bos" or "steps"), the rng state after its
-    last draw, and with keep_logits the logits each pick was made from (one row per pick, the BOS pick included)."""
+    last draw, with keep_logits the logits each pick was made from (one row per pick, the BOS pick included), and with logprobs=k one
+    (lp, [(id, lp), ... k]) per pick: the pick's log-probability and the k most likely tokens'."""
 
-    __slots__ = ("tokens_fed", "finish", "rng_state", "logits")
+    __slots__ = ("tokens_fed", "finish", "rng_state", "logits", "logprobs")
 
-    def __init__(self, tokens_fed, finish, rng_state, logits=None):
+    def __init__(self, tokens_fed, finish, rng_state, logits=None, logprobs=None):
         self.tokens_fed, self.finish, self.rng_state, self.logits = tokens_fed, finish, rng_state, logits
+        self.logprobs = logprobs
 
     def __repr__(self):
         return "Result(tokens_fed=%d tokens, finish=%r, rng_state=%d)" % (len(self.tokens_fed), self.finish, self.rng_state)
 
 
 class _Request:
-    def __init__(self, rid, prompt, steps, temperature, topp, seed):
+    def __init__(self, rid, prompt, steps, temperature, topp, seed, logprobs=None):
         self.rid = rid
         stop = prompt.index(BOS) if BOS in prompt else -1      # a forced BOS ends the reference's loop there (llama2.ts:497)
         self.prompt = prompt if stop < 0 else prompt[:stop]
@@ -45,6 +51,8 @@ class _Request:
         self.fed = []                           # tokens fed so far; the next one goes to position len(fed)
         self.next = None                        # the next token to feed once the prompt is done (a pick)
         self.logits = []
+        self.top = None if logprobs is None else int(logprobs)
+        self.logprobs = []
 
     @property
     def in_prompt(self):
@@ -69,16 +77,19 @@ class Scheduler:
         self._next_id = 0
         self.calls = 0
 
-    def submit(self, prompt_ids, steps, temperature=0.0, topp=1.0, seed=1):
-        """Queue one request; returns its id.  steps <= seq_len (the reference's clamp is the caller's)."""
+    def submit(self, prompt_ids, steps, temperature=0.0, topp=1.0, seed=1, logprobs=None):
+        """Queue one request; returns its id.  steps <= seq_len (the reference's clamp is the caller's).  logprobs: None, or k in
+        0 .. 20 -- the log-probability of each pick and the k most likely tokens' (Result.logprobs)."""
         steps = int(steps)
         if steps < 0 or steps > self.seq_len:
             raise ValueError("steps %d outside [0, seq_len=%d]" % (steps, self.seq_len))
         if temperature != temperature or topp != topp:
             raise ValueError("temperature / topp is NaN")
+        if logprobs is not None and not 0 <= int(logprobs) <= 20:
+            raise ValueError("logprobs %d outside [0, 20]" % int(logprobs))
         rid = self._next_id
         self._next_id += 1
-        self.waiting.append(_Request(rid, [int(t) for t in prompt_ids], steps, temperature, topp, seed))
+        self.waiting.append(_Request(rid, [int(t) for t in prompt_ids], steps, temperature, topp, seed, logprobs))
         return rid
 
     @property
@@ -86,7 +97,7 @@ class Scheduler:
         return not self.waiting and not self.active
 
     def _finish(self, r, how, done):
-        res = Result(r.fed, how, r.rng, r.logits if self.keep_logits else None)
+        res = Result(r.fed, how, r.rng, r.logits if self.keep_logits else None, None if r.top is None else r.logprobs)
         self.results[r.rid] = done[r.rid] = res
         if r.slot is not None:
             self.active.remove(r)
@@ -126,10 +137,13 @@ class Scheduler:
         temp = [r.temperature if real else 0.0 for r, _, _, real in rows]
         topp = [r.topp for r, _, _, _ in rows]
         rng = [r.rng for r, _, _, _ in rows]
+        ks = [r.top for r, _, _, _ in rows if r.top is not None]
+        extra = {"logprobs": max(ks)} if ks else {}
         out = self.ctx.step_batch(seqs, [t for _, t, _, _ in rows], [p for _, _, p, _ in rows], temperature=temp, topp=topp, rng=rng,
-                                  logits=self.keep_logits)
+                                  logits=self.keep_logits, **extra)
         self.calls += 1
         picks, rng_after = out[0], out[1]
+        lps = out[-1] if ks else None
         for i, (r, toks, p, real) in enumerate(rows):
             r.fed.extend(toks)
             if real:
@@ -137,6 +151,8 @@ class Scheduler:
                     r.rng = int(rng_after[i])
                 if self.keep_logits:
                     r.logits.append(out[2][i])
+                if r.top is not None:
+                    r.logprobs.append((float(lps[0][i]), [(int(lps[1][i][q]), float(lps[2][i][q])) for q in range(r.top)]))
                 nxt = int(picks[i])
             elif r.in_prompt:
                 nxt = r.known[len(r.fed)]
