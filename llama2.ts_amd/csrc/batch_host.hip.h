@@ -1,5 +1,8 @@
 // batch_host.hip.h -- host side of batched decode (batch.hip.h): l2_seq_reserve, l2_seq_prefill, l2_seq_prefill_batch, l2_forward_batch,
 // l2_decode_greedy_batch, l2_decode_sample_batch, l2_step_batch, l2_seq_score_batch, l2_step_batch_logprobs, l2_read_seq_cache, l2_seq_fork.
+// The batch step (bt_forward) and the packed launch sequences (bp_enqueue) are prefill_host.hip.h's pf_layers with row tables, their own
+// activation sets and attention; what they share -- argument checks, the row classifier, the decode-form attention, the row sampler's
+// staging and read-back -- is one helper each, here.
 // Part of the one translation unit llama2_hip.hip (included there, in order); not a stand-alone header.
 #pragma once
 
@@ -18,14 +21,15 @@ struct BatchState {
   int* tab = nullptr;                     // device [4][BT_MAX]: sequence, token, position, start position of every row
   int* h_tab = nullptr;                   // pinned staging of tab
   int* out = nullptr;                     // device [BT_MAX][S]: tokens picked by row r at position p -> out[r][p - start[r]]
-  float *x = nullptr, *xn = nullptr, *q = nullptr, *xb = nullptr, *hb = nullptr, *logits = nullptr;   // [BT_MAX][d | h | V]
+  PfActs act;                             // [BT_MAX] rows: the batch step's activations
+  float* logits = nullptr;                // [BT_MAX][V]
   hipGraphExec_t g[BT_MAX + 1] = {};      // the recorded step per row count
   hipGraphExec_t gs[BT_MAX + 1] = {};     // the recorded sampled step per row count (forward + row sampler + bt_pick_kernel)
   l2s::BatchSampler* smp = nullptr;       // the row sampler's buffers: allocated at the first l2_decode_sample_batch
   unsigned long long smp_stats[2] = {};   // {tokens sampled, of those by the serial loop} over every l2_decode_sample_batch
   std::vector<uintptr_t> sig;             // what the recorded steps baked in (weight addresses, options)
   // Packed prompts (l2_seq_prefill_batch), allocated at its first call: activations of one launch sequence, and the call's tables
-  float *px = nullptr, *pxn = nullptr, *pq = nullptr, *pxb = nullptr, *phb = nullptr;   // [BP_ROWS][d | max(d, h) | d | d | h]
+  PfActs pact;                            // [BP_ROWS] rows
   int* ptab = nullptr;                    // device: bp_tables' layout, ptab_cap ints
   size_t ptab_cap = 0;
   // Log-probabilities (logprob.hip.h), allocated at the first call that asks for them
@@ -48,8 +52,8 @@ static void batch_free(l2_ctx* c) {
   if (!b) return;
   bt_drop_graphs(b);
   for (size_t s = 1; s < b->kc.size(); ++s) { if (b->kc[s]) hipFree(b->kc[s]); if (b->vc[s]) hipFree(b->vc[s]); }
-  void* dev[] = {b->d_kc, b->d_vc, b->tab, b->out, b->x, b->xn, b->q, b->xb, b->hb, b->logits, b->px, b->pxn, b->pq, b->pxb, b->phb, b->ptab,
-                 b->slogits, b->lpbuf};
+  void* dev[] = {b->d_kc, b->d_vc, b->tab, b->out, b->act.x, b->act.xn, b->act.q, b->act.xb, b->act.hb, b->logits, b->pact.x, b->pact.xn, b->pact.q,
+                 b->pact.xb, b->pact.hb, b->ptab, b->slogits, b->lpbuf};
   for (void* p : dev) if (p) hipFree(p);
   if (b->h_tab) hipHostFree(b->h_tab);
   if (b->smp) { l2s::destroy_rows(b->smp); delete b->smp; }
@@ -84,8 +88,8 @@ extern "C" int l2_seq_reserve(l2_ctx* c, int n_seqs) {
   for (int s = 1; s < n_seqs; ++s) { dev((void**)&b->kc[s], slab); dev((void**)&b->vc[s], slab); }
   dev((void**)&b->d_kc, R * sizeof(float*)); dev((void**)&b->d_vc, R * sizeof(float*));
   dev((void**)&b->tab, 4 * R * sizeof(int)); dev((void**)&b->out, R * c->S * sizeof(int));
-  dev((void**)&b->x, R * c->d * 4); dev((void**)&b->xn, R * wide * 4); dev((void**)&b->q, R * c->d * 4);
-  dev((void**)&b->xb, R * c->d * 4); dev((void**)&b->hb, R * c->h * 4); dev((void**)&b->logits, R * c->V * 4);
+  dev((void**)&b->act.x, R * c->d * 4); dev((void**)&b->act.xn, R * wide * 4); dev((void**)&b->act.q, R * c->d * 4);
+  dev((void**)&b->act.xb, R * c->d * 4); dev((void**)&b->act.hb, R * c->h * 4); dev((void**)&b->logits, R * c->V * 4);
   if (ok && hipHostMalloc((void**)&b->h_tab, 4 * R * sizeof(int), 0) != hipSuccess) ok = false;
   if (ok) {
     float* tk[BT_MAX] = {}; float* tv[BT_MAX] = {};
@@ -100,31 +104,60 @@ extern "C" int l2_seq_reserve(l2_ctx* c, int n_seqs) {
   return L2_OK;
 }
 
+// A sequence's next position (L2_OPT_CHECK_POS: cache rows 0 .. next - 1 have been written); sequence 0's is the context's own.
+static int bt_next(const l2_ctx* c, int s) { return s == 0 ? c->next_pos : c->bt->next_pos[s]; }
+static void bt_set_next(l2_ctx* c, int s, int next) { if (s == 0) c->next_pos = next; else c->bt->next_pos[s] = next; }
+
+// What every batch call checks first: the context, its arrays (`arrays`: all of them given), the reserved sequences, n.
+static int bt_check_call(const l2_ctx* c, bool arrays, int n) {
+  if (!c) return fail(L2_E_ARG, "null context");
+  if (!arrays) return fail(L2_E_ARG, "null argument");
+  if (!c->bt) return fail(L2_E_STATE, "no sequences reserved: call l2_seq_reserve first");
+  if (n < 1 || n > c->bt->n_seqs) return fail(L2_E_ARG, "n = %d outside [1, n_seqs = %d]", n, c->bt->n_seqs);
+  return L2_OK;
+}
+
+// Row i of a call names sequence s: a reserved one, named by no earlier row (`seen`, [BT_MAX]).
+static int bt_check_seq(const BatchState* b, bool* seen, int i, int s) {
+  if (s < 0 || s >= b->n_seqs) return fail(L2_E_ARG, "row %d: sequence %d outside [0, n_seqs = %d)", i, s, b->n_seqs);
+  if (seen[s]) return fail(L2_E_ARG, "row %d: sequence %d appears twice in one call", i, s);
+  seen[s] = true;
+  return L2_OK;
+}
+
+// L2_CHECK_POS: a call may rewind or restart sequence s, not skip ahead of what it has written.
+static int bt_check_pos(const l2_ctx* c, int s, int pos) {
+  const int next = bt_next(c, s);
+  if (c->opt_pos_check && pos != 0 && pos > next)
+    return fail(L2_E_STATE, "L2_CHECK_POS: sequence %d, pos %d skips ahead of the sequence (cache rows 0 .. %d have been written)", s, pos, next - 1);
+  return L2_OK;
+}
+
 // Arguments of a batch call, all checked before anything touches the GPU.
 static int bt_check(l2_ctx* c, int n, const int32_t* seqs, const int32_t* tokens, const int32_t* pos, int steps) {
-  if (!c) return fail(L2_E_ARG, "null context");
-  if (!seqs || !tokens || !pos) return fail(L2_E_ARG, "null argument");
-  if (!c->bt) return fail(L2_E_STATE, "no sequences reserved: call l2_seq_reserve first");
-  const BatchState* b = c->bt;
-  if (n < 1 || n > b->n_seqs) return fail(L2_E_ARG, "n = %d outside [1, n_seqs = %d]", n, b->n_seqs);
+  if (int rc = bt_check_call(c, seqs && tokens && pos, n)) return rc;
   if (steps < 0) return fail(L2_E_ARG, "steps %d < 0", steps);
   bool seen[BT_MAX] = {};
   for (int i = 0; i < n; ++i) {
-    const int s = seqs[i];
-    if (s < 0 || s >= b->n_seqs) return fail(L2_E_ARG, "row %d: sequence %d outside [0, n_seqs = %d)", i, s, b->n_seqs);
-    if (seen[s]) return fail(L2_E_ARG, "row %d: sequence %d appears twice in one call", i, s);
-    seen[s] = true;
+    if (int rc = bt_check_seq(c->bt, seen, i, seqs[i])) return rc;
     if (tokens[i] < 0 || tokens[i] >= c->V) return fail(L2_E_ARG, "row %d: token %d outside [0, vocab_size=%d)", i, tokens[i], c->V);
     if (pos[i] < 0 || pos[i] >= c->S) return fail(L2_E_ARG, "row %d: pos %d outside [0, seq_len=%d)", i, pos[i], c->S);
     if (pos[i] + (steps > 0 ? steps : 1) > c->S) return fail(L2_E_ARG, "row %d: pos %d + steps %d runs past seq_len=%d", i, pos[i], steps, c->S);
-    const int next = s == 0 ? c->next_pos : b->next_pos[s];
-    if (c->opt_pos_check && pos[i] != 0 && pos[i] > next)
-      return fail(L2_E_STATE, "L2_CHECK_POS: sequence %d, pos %d skips ahead of the sequence (cache rows 0 .. %d have been written)", s, pos[i], next - 1);
+    if (int rc = bt_check_pos(c, seqs[i], pos[i])) return rc;
   }
   return L2_OK;
 }
 
-static void bt_set_next(l2_ctx* c, int s, int next) { if (s == 0) c->next_pos = next; else c->bt->next_pos[s] = next; }
+// Per-row sampling settings (null: every row greedy): no NaN, and -- when a row draws (*any) -- a vocabulary the row sampler can hold.
+static int bt_check_sampling(const l2_ctx* c, int n, const double* temperature, const double* topp, bool* any) {
+  *any = false;
+  for (int i = 0; temperature && i < n; ++i) {
+    if (!(temperature[i] == temperature[i]) || !(topp[i] == topp[i])) return fail(L2_E_ARG, "row %d: temperature / topp is NaN", i);
+    if (temperature[i] != 0.0) *any = true;
+  }
+  if (*any && c->V > l2s::MAX_VOCAB) return fail(L2_E_CONFIG, "device sampler supports vocabularies up to %d", (int)l2s::MAX_VOCAB);
+  return L2_OK;
+}
 
 // Weights of the batch classifier: the row-major matrix (wcls, or the embedding table when shared), or -- once wcls has been given back
 // -- the decode classifier's repacked copy.
@@ -136,18 +169,6 @@ static void bt_cls_weights(const l2_ctx* c, PfArgs& a) {
     return;
   }
   a.w0 = c->w[L2_T_WCLS];
-}
-
-// One batch GEMM: the register-blocked form where prefill takes it for one 64-row chunk, else one 16-row weight tile per workgroup.
-template <int MODE>
-static void bt_gemm(const l2_ctx* c, const PfArgs& a, int tt, hipStream_t st) {
-  if constexpr (MODE == MODE_WO || MODE == MODE_W13 || MODE == MODE_W2) {
-    if (pf3_ok(c) && tt == 4) { launch_pf3<MODE, 1>(a, 1, st); return; }
-  }
-  const dim3 grid((a.rows + 15) / 16);
-  if (tt == 4) hipLaunchKernelGGL((pf_gemm_kernel<MODE, 4, 4>), grid, dim3(256), 0, st, a);
-  else if (tt == 2) hipLaunchKernelGGL((pf_gemm_kernel<MODE, 4, 2>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((pf_gemm_kernel<MODE, 4, 1>), grid, dim3(256), 0, st, a);
 }
 
 static hipError_t launch_bt_attn(const l2_ctx* c, const AttnArgs& a, const AttnRows& r, int n, hipStream_t st) {
@@ -167,76 +188,63 @@ static hipError_t launch_bt_attn(const l2_ctx* c, const AttnArgs& a, const AttnR
   return hipGetLastError();
 }
 
+// Attention in the decode form, one workgroup per (head, row), over n rows of the row tables `r` at layer l (its slab loff floats into a
+// sequence's cache): A.q -> A.xb, each row over its own sequence's cache (llama2.ts:244-267).
+static int bt_attn_rows(const l2_ctx* c, int l, const PfActs& A, const AttnRows& r, size_t loff, int n, hipStream_t st) {
+  AttnArgs aa;
+  fill_attn_args(c, l, aa);      // (its split count is the single-sequence step's: the kernel runs one workgroup per (head, row), one split)
+  aa.q = A.q; aa.xb = A.xb; aa.att = nullptr; aa.tokpos = nullptr; aa.part = nullptr; aa.counter = nullptr;
+  const AttnRows ar = {r.seq, r.pos, r.kc, r.vc, loff};
+  LCHK(launch_bt_attn(c, aa, ar, n, st));
+  return L2_OK;
+}
+
+// Final rmsnorm + classifier (llama2.ts:299-302): the residual rows `x` normed into `xn` (norm_rows of them: what the caller's launch
+// sequence holds, padding included), then the logits of the first n into out [n][V], 64 rows (pf_gemm_kernel<MODE_CLS_ROWS>'s four tiles) a slice.
+static int bt_classify(const l2_ctx* c, const float* x, float* xn, float* out, int norm_rows, int n, hipStream_t st) {
+  hipLaunchKernelGGL(pf_norm_kernel, dim3(norm_rows), dim3(256), 0, st, xn, x, c->w[L2_T_RMS_FINAL], c->d);
+  for (int s0 = 0; s0 < n; s0 += PF_T) {
+    const int ms = std::min(n - s0, (int)PF_T);
+    PfArgs a;
+    memset(&a, 0, sizeof(a));
+    bt_cls_weights(c, a);
+    a.xin = xn + (size_t)s0 * c->d; a.out = out + (size_t)s0 * c->V; a.n = c->d; a.rows = c->V; a.dim = c->d; a.nvalid = ms;
+    bt_gemm<MODE_CLS_ROWS>(c, a, pf_tiles(ms).tt, st);
+  }
+  LCHK(hipGetLastError());
+  return L2_OK;
+}
+
 // The forward part of one batch step of n rows (tables already on the device): embed, the layers, final norm, classifier -> b->logits.
 static int bt_forward(l2_ctx* c, int n, hipStream_t st) {
   BatchState* b = c->bt;
-  const int tt = (n > 32) ? 4 : (n > 16) ? 2 : 1, nt = 16 * tt;      // token rows the kernels see (whole 16-row MFMA tiles)
-  const size_t d = c->d;
-  hipLaunchKernelGGL(pf_embed_kernel, dim3(nt), dim3(256), 0, st, b->x, c->w[L2_T_TOKEN_EMBEDDING], (const int*)b->tok_of(), c->d, n);
-  LCHK(hipGetLastError());
-  for (int l = 0; l < c->L; ++l) {
-    const size_t loff = (size_t)l * c->S * c->d;
-    PfArgs a;
-    memset(&a, 0, sizeof(a));
-    a.fr = c->w[L2_T_FREQ_REAL]; a.fi = c->w[L2_T_FREQ_IMAG]; a.head_size = c->hs; a.dim = c->d; a.pos0 = 0; a.nvalid = n;
-    a.x = b->x;
-    a.row_seq = b->seq_of(); a.row_pos = b->pos_of(); a.seq_kc = b->d_kc; a.seq_vc = b->d_vc; a.seq_loff = loff;
-    // rmsnorm + q,k,v + RoPE + every row's cache row (llama2.ts:216-240)
-    hipLaunchKernelGGL(pf_norm_kernel, dim3(nt), dim3(256), 0, st, b->xn, b->x, c->w[L2_T_RMS_ATT] + d * l, c->d);
-    pf_weights<MODE_QKV>(c, l, a, L2_T_WQ, L2_T_WK, L2_T_WV);
-    a.xin = b->xn; a.out = b->q; a.n = c->d; a.rows = 3 * c->d;
-    bt_gemm<MODE_QKV_ROWS>(c, a, tt, st);
-    LCHK(hipGetLastError());
-    // attention, one workgroup per (head, row) over the row's own cache (llama2.ts:244-267)
-    AttnArgs aa;
-    fill_attn_args(c, l, aa);      // (its split count is the single-sequence step's: the kernel runs one workgroup per (head, row))
-    aa.q = b->q; aa.xb = b->xb; aa.att = nullptr; aa.tokpos = nullptr; aa.part = nullptr; aa.counter = nullptr;
-    AttnRows ar = {b->seq_of(), b->pos_of(), b->d_kc, b->d_vc, loff};
-    LCHK(launch_bt_attn(c, aa, ar, n, st));
-    // wo + residual (llama2.ts:270-273)
-    pf_weights<MODE_WO>(c, l, a, L2_T_WO, -1, -1); a.xin = b->xb; a.n = c->d; a.rows = c->d;
-    bt_gemm<MODE_WO>(c, a, tt, st);
-    // rmsnorm + w1,w3 + SwiGLU (llama2.ts:276-289)
-    hipLaunchKernelGGL(pf_norm_kernel, dim3(nt), dim3(256), 0, st, b->xn, b->x, c->w[L2_T_RMS_FFN] + d * l, c->d);
-    pf_weights<MODE_W13>(c, l, a, L2_T_W1, L2_T_W3, -1);
-    a.xin = b->xn; a.out = b->hb; a.n = c->d; a.rows = c->h;
-    bt_gemm<MODE_W13>(c, a, tt, st);
-    // w2 + residual (llama2.ts:292-295)
-    pf_weights<MODE_W2>(c, l, a, L2_T_W2, -1, -1); a.xin = b->hb; a.n = c->h; a.rows = c->d;
-    bt_gemm<MODE_W2>(c, a, tt, st);
-    LCHK(hipGetLastError());
+  const AttnRows rows = {b->seq_of(), b->pos_of(), b->d_kc, b->d_vc, 0};
+  const auto attn = [&](int l, size_t loff) { return bt_attn_rows(c, l, b->act, rows, loff, n, st); };
+  const int rc = pf_layers<PF_GEMM_BATCH>(c, b->act, b->tok_of(), n, rows, attn, st);
+  if (rc) return rc;
+  return bt_classify(c, b->act.x, b->act.xn, b->logits, pf_tiles(n).nt, n, st);
+}
+
+// Every row's pick from b->logits into the token table (fed next) and b->out: its argmax (llama2.ts:364-366), or -- `sampled` -- the row
+// sampler (every phase once for all n rows), then every row's pick applied.
+static int bt_enqueue_pick(l2_ctx* c, int n, bool sampled, hipStream_t st) {
+  BatchState* b = c->bt;
+  if (sampled) {
+    LCHK(l2s::enqueue_rows(*b->smp, b->logits, n, st));
+    hipLaunchKernelGGL(bt_pick_kernel, dim3(n), dim3(1024), 0, st, (const float*)b->logits, c->V, (const double*)b->smp->params, b->smp->pick,
+                       b->tok_of(), b->pos_of(), (const int*)b->start_of(), b->out, c->S);
+  } else {
+    hipLaunchKernelGGL(bt_argmax_kernel, dim3(n), dim3(1024), 0, st, (const float*)b->logits, c->V, b->tok_of(), b->pos_of(), (const int*)b->start_of(),
+                       b->out, c->S);
   }
-  // final rmsnorm + classifier (llama2.ts:299-302): logits [row][V]
-  hipLaunchKernelGGL(pf_norm_kernel, dim3(nt), dim3(256), 0, st, b->xn, b->x, c->w[L2_T_RMS_FINAL], c->d);
-  PfArgs a;
-  memset(&a, 0, sizeof(a));
-  bt_cls_weights(c, a);
-  a.xin = b->xn; a.out = b->logits; a.n = c->d; a.rows = c->V; a.dim = c->d; a.nvalid = n;
-  bt_gemm<MODE_CLS_ROWS>(c, a, tt, st);
   LCHK(hipGetLastError());
   return L2_OK;
 }
 
-// One greedy batch step: the forward part, then every row's argmax (llama2.ts:364-366), fed next.
-static int bt_enqueue(l2_ctx* c, int n, hipStream_t st) {
-  BatchState* b = c->bt;
-  int rc = bt_forward(c, n, st);
-  if (rc) return rc;
-  hipLaunchKernelGGL(bt_argmax_kernel, dim3(n), dim3(1024), 0, st, (const float*)b->logits, c->V, b->tok_of(), b->pos_of(), (const int*)b->start_of(), b->out, c->S);
-  LCHK(hipGetLastError());
-  return L2_OK;
-}
-
-// One sampled batch step: the same forward part, the row sampler (every phase once for all n rows), then every row's pick applied.
-static int bt_enqueue_sampled(l2_ctx* c, int n, hipStream_t st) {
-  BatchState* b = c->bt;
-  int rc = bt_forward(c, n, st);
-  if (rc) return rc;
-  LCHK(l2s::enqueue_rows(*b->smp, b->logits, n, st));
-  hipLaunchKernelGGL(bt_pick_kernel, dim3(n), dim3(1024), 0, st, (const float*)b->logits, c->V, (const double*)b->smp->params, b->smp->pick,
-                     b->tok_of(), b->pos_of(), (const int*)b->start_of(), b->out, c->S);
-  LCHK(hipGetLastError());
-  return L2_OK;
+// One batch step, greedy or sampled: the forward part, then every row's pick.
+static int bt_enqueue(l2_ctx* c, int n, bool sampled, hipStream_t st) {
+  const int rc = bt_forward(c, n, st);
+  return rc ? rc : bt_enqueue_pick(c, n, sampled, st);
 }
 
 // What a recorded step baked in: every weight address it may read and the options that shape it.  A change drops the recordings.
@@ -248,10 +256,42 @@ static std::vector<uintptr_t> bt_signature(const l2_ctx* c) {
   return s;
 }
 
+// The per-row sampling arguments of a call, in call order.
+struct BtSampling { const double *temperature, *topp; uint64_t* rng_state; };
+
+// Stage the settings and rng states of n rows (row j: the call's row ord[j]; null: j) in the row sampler's pinned tables -- the stream has
+// been synchronised since the previous call's copies -- and upload them.
+static int bt_sampler_upload(const l2s::BatchSampler& sm, int n, const BtSampling& s, const int* ord, hipStream_t st) {
+  for (int j = 0; j < n; ++j) {
+    const int i = ord ? ord[j] : j;
+    sm.h_params[2 * j] = s.temperature[i]; sm.h_params[2 * j + 1] = s.topp[i]; sm.h_rng[j] = s.rng_state[i];
+  }
+  HIPCHK(l2s::reset_rows(sm, n, st));      // "zero between tokens" holds whatever an earlier (aborted) call left
+  HIPCHK(hipMemcpyAsync(sm.params, sm.h_params, 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(sm.rng, sm.h_rng, (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+  return L2_OK;
+}
+
+// The way back: enqueue the copies of the rows' rng states and counters into the pinned tables ...
+static int bt_sampler_fetch(const l2s::BatchSampler& sm, int n, hipStream_t st) {
+  HIPCHK(hipMemcpyAsync(sm.h_rng, sm.rng, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(sm.h_stats, sm.stats, 2 * (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  return L2_OK;
+}
+
+// ... and, once the stream has been synchronised, hand the states to the caller and add the counters to smp_stats (saturating).
+static void bt_sampler_finish(BatchState* b, int n, uint64_t* rng_state, const int* ord) {
+  for (int j = 0; j < n; ++j) {
+    rng_state[ord ? ord[j] : j] = b->smp->h_rng[j];
+    for (int k = 0; k < 2; ++k) { const unsigned long long v = b->smp_stats[k] + b->smp->h_stats[2 * j + k]; b->smp_stats[k] = v < b->smp_stats[k] ? ~0ull : v; }
+  }
+}
+
 // Upload the tables of n rows and run `steps` batch steps (recorded once per row count, replayed; eager with L2_OPT_USE_GRAPH = 0).
-// `sampled`: the sampled step, whose per-row settings and rng states the caller has staged in b->smp's pinned tables.
-static int bt_run(l2_ctx* c, int n, const int32_t* seqs, const int32_t* tokens, const int32_t* pos, int steps, bool sampled = false) {
+// `smp`: the sampled step with these per-row settings (the caller has made b->smp); their rng states come back advanced.
+static int bt_run(l2_ctx* c, int n, const int32_t* seqs, const int32_t* tokens, const int32_t* pos, int steps, const BtSampling* smp = nullptr) {
   BatchState* b = c->bt;
+  const bool sampled = smp != nullptr;
   int rc = ensure_ready(c);
   if (rc) return rc;
   HIPCHK(hipSetDevice(c->device));
@@ -266,18 +306,12 @@ static int bt_run(l2_ctx* c, int n, const int32_t* seqs, const int32_t* tokens, 
     b->h_tab[3 * BT_MAX + i] = live ? pos[i] : 0;
   }
   HIPCHK(hipMemcpyAsync(b->tab, b->h_tab, 4 * BT_MAX * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  if (sampled) {
-    const l2s::BatchSampler& sm = *b->smp;
-    HIPCHK(l2s::reset_rows(sm, n, c->stream));      // "zero between tokens" holds whatever an earlier (aborted) call left
-    HIPCHK(hipMemcpyAsync(sm.params, sm.h_params, 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(sm.rng, sm.h_rng, (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
-  }
+  if (sampled) { rc = bt_sampler_upload(*b->smp, n, *smp, nullptr, c->stream); if (rc) return rc; }
   hipGraphExec_t* rec = sampled ? b->gs : b->g;
-  auto enqueue = sampled ? bt_enqueue_sampled : bt_enqueue;
   if (c->opt_graph && !rec[n]) {
     hipGraph_t graph = nullptr;
     LCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    rc = enqueue(c, n, c->stream);
+    rc = bt_enqueue(c, n, sampled, c->stream);
     const hipError_t e = hipStreamEndCapture(c->stream, &graph);
     if (rc) { if (graph) hipGraphDestroy(graph); return rc; }
     if (e != hipSuccess) return fail(L2_E_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
@@ -287,9 +321,11 @@ static int bt_run(l2_ctx* c, int n, const int32_t* seqs, const int32_t* tokens, 
   }
   for (int s = 0; s < steps; ++s) {
     if (c->opt_graph) HIPCHK(hipGraphLaunch(rec[n], c->stream));
-    else { rc = enqueue(c, n, c->stream); if (rc) return rc; }
+    else { rc = bt_enqueue(c, n, sampled, c->stream); if (rc) return rc; }
   }
+  if (sampled) { rc = bt_sampler_fetch(*b->smp, n, c->stream); if (rc) return rc; }
   HIPCHK(hipStreamSynchronize(c->stream));
+  if (sampled) bt_sampler_finish(b, n, smp->rng_state, nullptr);
   for (int i = 0; i < n; ++i) bt_set_next(c, seqs[i], pos[i] + steps);
   return L2_OK;
 }
@@ -303,6 +339,12 @@ extern "C" int l2_forward_batch(l2_ctx* c, int n, const int32_t* seqs, const int
   return L2_OK;
 }
 
+// Every row's picks of `steps` steps (b->out [row][S]) into tokens_out [n][steps].
+static int bt_copy_tokens(const l2_ctx* c, int32_t* tokens_out, int steps, int n) {
+  HIPCHK(hipMemcpy2D(tokens_out, (size_t)steps * sizeof(int32_t), c->bt->out, (size_t)c->S * sizeof(int), (size_t)steps * sizeof(int32_t), n, hipMemcpyDeviceToHost));
+  return L2_OK;
+}
+
 extern "C" int l2_decode_greedy_batch(l2_ctx* c, int n, const int32_t* seqs, const int32_t* first_tokens, const int32_t* pos0, int steps,
                                       int32_t* tokens_out) {
   int rc = bt_check(c, n, seqs, first_tokens, pos0, steps);
@@ -311,8 +353,7 @@ extern "C" int l2_decode_greedy_batch(l2_ctx* c, int n, const int32_t* seqs, con
   if (steps == 0) return L2_OK;
   rc = bt_run(c, n, seqs, first_tokens, pos0, steps);
   if (rc) return rc;
-  HIPCHK(hipMemcpy2D(tokens_out, (size_t)steps * sizeof(int32_t), c->bt->out, (size_t)c->S * sizeof(int), (size_t)steps * sizeof(int32_t), n, hipMemcpyDeviceToHost));
-  return L2_OK;
+  return bt_copy_tokens(c, tokens_out, steps, n);
 }
 
 // The row sampler's buffers (one row per reserved sequence), allocated at the first call that samples.
@@ -333,35 +374,20 @@ extern "C" int l2_decode_sample_batch(l2_ctx* c, int n, const int32_t* seqs, con
   if (!temperature || !topp || !rng_state) return fail(L2_E_ARG, "null temperature / topp / rng_state");
   if (!tokens_out && steps > 0) return fail(L2_E_ARG, "null tokens_out");
   bool any = false;
-  for (int i = 0; i < n; ++i) {
-    if (!(temperature[i] == temperature[i]) || !(topp[i] == topp[i])) return fail(L2_E_ARG, "row %d: temperature / topp is NaN", i);
-    if (temperature[i] != 0.0) any = true;
-  }
-  if (any && c->V > l2s::MAX_VOCAB) return fail(L2_E_CONFIG, "device sampler supports vocabularies up to %d", (int)l2s::MAX_VOCAB);
+  rc = bt_check_sampling(c, n, temperature, topp, &any);
+  if (rc) return rc;
   if (steps == 0) return L2_OK;
-  BatchState* b = c->bt;
-  if (c->V > l2s::MAX_VOCAB) {      // every row greedy (no draw, rng states untouched) on a vocabulary the row sampler cannot hold
-    rc = bt_run(c, n, seqs, first_tokens, pos0, steps);
+  const BtSampling smp = {temperature, topp, rng_state};
+  const bool sampler = c->V <= l2s::MAX_VOCAB;      // else every row greedy (no draw, rng states untouched) on a vocabulary the row sampler cannot hold
+  if (sampler) {
+    HIPCHK(hipSetDevice(c->device));
+    rc = bt_ensure_sampler(c, "l2_decode_sample_batch");
     if (rc) return rc;
-    HIPCHK(hipMemcpy2D(tokens_out, (size_t)steps * sizeof(int32_t), b->out, (size_t)c->S * sizeof(int), (size_t)steps * sizeof(int32_t), n, hipMemcpyDeviceToHost));
-    return L2_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));      // (the pinned tables: the previous call's copies have completed)
   }
-  HIPCHK(hipSetDevice(c->device));
-  rc = bt_ensure_sampler(c, "l2_decode_sample_batch");
+  rc = bt_run(c, n, seqs, first_tokens, pos0, steps, sampler ? &smp : nullptr);
   if (rc) return rc;
-  l2s::BatchSampler& sm = *b->smp;
-  HIPCHK(hipStreamSynchronize(c->stream));      // (the pinned tables: the previous call's copies have completed)
-  for (int i = 0; i < n; ++i) { sm.h_params[2 * i] = temperature[i]; sm.h_params[2 * i + 1] = topp[i]; sm.h_rng[i] = rng_state[i]; }
-  rc = bt_run(c, n, seqs, first_tokens, pos0, steps, true);
-  if (rc) return rc;
-  HIPCHK(hipMemcpy2D(tokens_out, (size_t)steps * sizeof(int32_t), b->out, (size_t)c->S * sizeof(int), (size_t)steps * sizeof(int32_t), n, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(sm.h_rng, sm.rng, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(sm.h_stats, sm.stats, 2 * (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  for (int i = 0; i < n; ++i) {
-    rng_state[i] = sm.h_rng[i];
-    for (int k = 0; k < 2; ++k) { const unsigned long long v = b->smp_stats[k] + sm.h_stats[2 * i + k]; b->smp_stats[k] = v < b->smp_stats[k] ? ~0ull : v; }
-  }
-  return L2_OK;
+  return bt_copy_tokens(c, tokens_out, steps, n);
 }
 
 extern "C" int l2_seq_prefill(l2_ctx* c, int seq, const int32_t* tokens, int n_tokens, int pos0, float* logits_out) {
@@ -372,8 +398,7 @@ extern "C" int l2_seq_prefill(l2_ctx* c, int seq, const int32_t* tokens, int n_t
   if (seq == 0) return l2_prefill(c, tokens, n_tokens, pos0, logits_out);
   if (n_tokens <= 0 || pos0 < 0 || pos0 + n_tokens > c->S) return fail(L2_E_ARG, "positions %d..%d outside [0, seq_len=%d)", pos0, pos0 + n_tokens - 1, c->S);
   for (int i = 0; i < n_tokens; ++i) if (tokens[i] < 0 || tokens[i] >= c->V) return fail(L2_E_ARG, "token %d outside [0, vocab_size=%d)", tokens[i], c->V);
-  if (c->opt_pos_check && pos0 != 0 && pos0 > b->next_pos[seq])
-    return fail(L2_E_STATE, "L2_CHECK_POS: sequence %d, pos %d skips ahead of the sequence (cache rows 0 .. %d have been written)", seq, pos0, b->next_pos[seq] - 1);
+  if (int rc = bt_check_pos(c, seq, pos0)) return rc;
   if (n_tokens == 1) {      // one row: the batch step
     const int32_t s1[1] = {seq}, t1[1] = {tokens[0]}, p1[1] = {pos0};
     return l2_forward_batch(c, 1, s1, t1, p1, logits_out);
@@ -391,14 +416,8 @@ extern "C" int l2_seq_prefill(l2_ctx* c, int seq, const int32_t* tokens, int n_t
   }
   if (pos0 + n_tokens > b->next_pos[seq] || pos0 == 0) b->next_pos[seq] = pos0 + n_tokens;
   if (logits_out) {      // the last position's logits: final norm of its row and the batch classifier (the context's own buffers stay as they are)
-    const int last = (n_tokens - 1) % step;
-    hipLaunchKernelGGL(pf_norm_kernel, dim3(1), dim3(256), 0, c->stream, b->xn, (const float*)(c->pf_x + (size_t)last * c->d), c->w[L2_T_RMS_FINAL], c->d);
-    PfArgs a;
-    memset(&a, 0, sizeof(a));
-    bt_cls_weights(c, a);
-    a.xin = b->xn; a.out = b->logits; a.n = c->d; a.rows = c->V; a.dim = c->d; a.nvalid = 1;
-    bt_gemm<MODE_CLS_ROWS>(c, a, 1, c->stream);
-    LCHK(hipGetLastError());
+    rc = bt_classify(c, c->pf.x + (size_t)((n_tokens - 1) % step) * c->d, b->act.xn, b->logits, 1, 1, c->stream);
+    if (rc) return rc;
     HIPCHK(hipMemcpyAsync(logits_out, b->logits, (size_t)c->V * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -407,38 +426,27 @@ extern "C" int l2_seq_prefill(l2_ctx* c, int seq, const int32_t* tokens, int n_t
 
 // ---- packed prompts (l2_seq_prefill_batch) and the mixed step (l2_step_batch) -----------------
 // The runs of a call are packed back to back, in packing order (row r: its sequence, position, token), and cut into launch sequences of up
-// to BP_ROWS rows where the register-blocked GEMMs apply, else PF_T rows (the 16-row-tile kernels): prefill_chunk's launch sequence over
-// them, with the per-row q / k / v epilogue and attention over ragged tiles (batch.hip.h: bp_attn_mfma_kernel).  A run may straddle
+// to BP_ROWS rows where the register-blocked GEMMs apply, else PF_T rows (the 16-row-tile kernels): prefill_chunk's launch sequence
+// (pf_layers) over them, with the per-row q / k / v epilogue and attention over ragged tiles (batch.hip.h: bp_attn_mfma_kernel).  A run may straddle
 // launch sequences: the later one reads the cache rows the earlier one stored.  Before the next launch sequence overwrites the residual
-// rows, those of the runs whose LAST row lies in this one are gathered into b->x (row i: run i); one final norm and one classifier over
+// rows, those of the runs whose LAST row lies in this one are gathered into b->act.x (row i: run i); one final norm and one classifier over
 // those n rows give the logits.  Device tables of the call (ints), one upload:
 //   [R] sequence, [R] position, [R] token of every row; [4 x tiles] every launch sequence's BpTiles; [n] gather rows (launch-relative)
 
 // Arguments of a packed call, all checked before anything touches the GPU; *R_out: the packed rows.
 static int bp_check(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0, size_t* R_out) {
-  if (!c) return fail(L2_E_ARG, "null context");
-  if (!seqs || !n_tokens || !tokens || !pos0) return fail(L2_E_ARG, "null argument");
-  if (!c->bt) return fail(L2_E_STATE, "no sequences reserved: call l2_seq_reserve first");
-  BatchState* b = c->bt;
-  if (n < 1 || n > b->n_seqs) return fail(L2_E_ARG, "n = %d outside [1, n_seqs = %d]", n, b->n_seqs);
+  if (int rc = bt_check_call(c, seqs && n_tokens && tokens && pos0, n)) return rc;
   bool seen[BT_MAX] = {};
   size_t R = 0;
   for (int i = 0; i < n; ++i) {
-    const int s = seqs[i];
-    if (s < 0 || s >= b->n_seqs) return fail(L2_E_ARG, "row %d: sequence %d outside [0, n_seqs = %d)", i, s, b->n_seqs);
-    if (seen[s]) return fail(L2_E_ARG, "row %d: sequence %d appears twice in one call", i, s);
-    seen[s] = true;
+    if (int rc = bt_check_seq(c->bt, seen, i, seqs[i])) return rc;
     if (n_tokens[i] < 1) return fail(L2_E_ARG, "row %d: n_tokens %d < 1", i, n_tokens[i]);
     if (pos0[i] < 0 || (long long)pos0[i] + n_tokens[i] > c->S)
       return fail(L2_E_ARG, "row %d: positions %d..%lld outside [0, seq_len=%d)", i, pos0[i], (long long)pos0[i] + n_tokens[i] - 1, c->S);
     R += (size_t)n_tokens[i];
   }
   for (size_t r = 0; r < R; ++r) if (tokens[r] < 0 || tokens[r] >= c->V) return fail(L2_E_ARG, "token %d (packed row %zu) outside [0, vocab_size=%d)", tokens[r], r, c->V);
-  for (int i = 0; i < n; ++i) {
-    const int s = seqs[i], next = s == 0 ? c->next_pos : b->next_pos[s];
-    if (c->opt_pos_check && pos0[i] != 0 && pos0[i] > next)
-      return fail(L2_E_STATE, "L2_CHECK_POS: sequence %d, pos %d skips ahead of the sequence (cache rows 0 .. %d have been written)", s, pos0[i], next - 1);
-  }
+  for (int i = 0; i < n; ++i) if (int rc = bt_check_pos(c, seqs[i], pos0[i])) return rc;
   *R_out = R;
   return L2_OK;
 }
@@ -484,172 +492,125 @@ static int lp_check_k(int top_k, const void* top_ids_out, const void* top_lp_out
   return L2_OK;
 }
 
-// Enqueue the launch sequences of n checked runs given in packing order (R rows in all).  The first nd runs are decode rows (one row
-// each, l2_step_batch; 0 for l2_seq_prefill_batch): they lie in the first launch sequence, are cut into no tile, and take the decode
-// attention form per (head, row) -- bt_attn_tile_kernel, at any head size and position -- while the tiles of the longer runs take
-// bp_attn_mfma_kernel with its LDS sized by the longest of them.  `logits`: gather every run's last row, final norm and classifier ->
-// b->logits rows 0 .. n-1.  htab holds the uploaded tables: the caller keeps it until the stream has been synchronised.  `score`
-// (l2_seq_score_batch): after each launch sequence's layers, the final norm and the classifier of EVERY row of it (pf_gemm_kernel
-// <MODE_CLS_ROWS> in 64-row slices: the last-row classifier's arithmetic) into b->slogits, then lp_rows_kernel over them with the
-// targets and outputs of `score` at the launch sequence's first row -- all before the next launch sequence overwrites the rows.
-static int bp_enqueue(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0, size_t R, int nd,
-                      bool logits, std::vector<int>& htab, const LpDev* score = nullptr, int top_k = 0) {
-  BatchState* b = c->bt;
-  hipStream_t st = c->stream;
-  const size_t d = c->d, h = c->h;
-  if (!b->px) {
-    HIPCHK(hipMalloc(&b->px, BP_ROWS * d * 4)); HIPCHK(hipMalloc(&b->pxn, BP_ROWS * (d > h ? d : h) * 4));
-    HIPCHK(hipMalloc(&b->pq, BP_ROWS * d * 4)); HIPCHK(hipMalloc(&b->pxb, BP_ROWS * d * 4)); HIPCHK(hipMalloc(&b->phb, BP_ROWS * h * 4));
-    HIPCHK(hipMemset(b->pxb, 0, BP_ROWS * d * 4)); HIPCHK(hipMemset(b->pq, 0, BP_ROWS * d * 4));
-  }
+// The plan of a packed call: host arithmetic on its arguments alone.
+struct BpPlan {
+  int step = 0, nl = 0;                        // rows of a launch sequence, launch sequences
+  size_t n_tiles = 0;                          // attention tiles of the call
+  std::vector<int> tile0, maxp, seq_a, seq_b;  // per launch sequence: its first tile ([nl + 1]), its tiles' highest pos0, the runs ending in it (seq_a .. seq_b - 1)
+  std::vector<int> htab;                       // the call's device tables (layout above) as uploaded: kept until the stream has been synchronised
+};
 
-  // ---- the plan: rows, launch sequences, their tiles and gathers
-  const int step = pf3_ok(c) ? (int)BP_ROWS : (int)PF_T;
+// Plan n checked runs given in packing order (R rows in all, launch sequences of `step`), the first nd of them decode rows: cut into no tile.
+static void bp_plan(BpPlan& p, int step, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0, size_t R, int nd) {
   const int nl = (int)((R + step - 1) / step);
+  p.step = step; p.nl = nl;
   std::vector<size_t> first(n + 1, 0);                       // first packed row of run i
   for (int i = 0; i < n; ++i) first[i + 1] = first[i] + (size_t)n_tokens[i];
   std::vector<BpTile> tiles;
-  std::vector<int> tile0(nl + 1, 0), maxp(nl, 0), seq_a(nl, 0), seq_b(nl, 0), gsrc(n, 0);
+  std::vector<int> gsrc(n, 0);
+  p.tile0.assign(nl + 1, 0); p.maxp.assign(nl, 0); p.seq_a.assign(nl, 0); p.seq_b.assign(nl, 0);
   for (int k = 0, i0 = 0; k < nl; ++k) {
     const size_t r0 = (size_t)k * step, r1 = std::min(r0 + step, R);
-    tile0[k] = (int)tiles.size();
-    seq_a[k] = i0;
+    p.tile0[k] = (int)tiles.size();
+    p.seq_a[k] = i0;
     for (int i = i0; i < n && first[i] < r1; ++i) {
       const size_t lo = std::max(first[i], r0), hi = std::min(first[i + 1], r1);
       for (size_t t = lo; t < hi && i >= nd; t += 16) {      // tiles start at the run's first row in this launch sequence
         const BpTile tl = {seqs[i], (int)(t - r0), pos0[i] + (int)(t - first[i]), (int)std::min<size_t>(16, hi - t)};
         tiles.push_back(tl);
-        maxp[k] = std::max(maxp[k], tl.pos0);
+        p.maxp[k] = std::max(p.maxp[k], tl.pos0);
       }
       if (first[i + 1] <= r1) { gsrc[i] = (int)(first[i + 1] - 1 - r0); i0 = i + 1; }      // its last row lies here
     }
-    seq_b[k] = i0;
-    std::sort(tiles.begin() + tile0[k], tiles.end(), [](const BpTile& x, const BpTile& y) { return x.pos0 > y.pos0; });   // longest first
+    p.seq_b[k] = i0;
+    std::sort(tiles.begin() + p.tile0[k], tiles.end(), [](const BpTile& x, const BpTile& y) { return x.pos0 > y.pos0; });   // longest first
   }
-  tile0[nl] = (int)tiles.size();
-  const size_t need = 3 * R + 4 * tiles.size() + (size_t)n;
-  htab.assign(need, 0);
+  p.tile0[nl] = (int)tiles.size();
+  p.n_tiles = tiles.size();
+  p.htab.assign(3 * R + 4 * tiles.size() + (size_t)n, 0);
   for (int i = 0; i < n; ++i)
-    for (int k = 0; k < n_tokens[i]; ++k) { const size_t r = first[i] + k; htab[r] = seqs[i]; htab[R + r] = pos0[i] + k; htab[2 * R + r] = tokens[r]; }
-  if (!tiles.empty()) memcpy(htab.data() + 3 * R, tiles.data(), tiles.size() * sizeof(BpTile));
-  memcpy(htab.data() + 3 * R + 4 * tiles.size(), gsrc.data(), (size_t)n * sizeof(int));
+    for (int k = 0; k < n_tokens[i]; ++k) { const size_t r = first[i] + k; p.htab[r] = seqs[i]; p.htab[R + r] = pos0[i] + k; p.htab[2 * R + r] = tokens[r]; }
+  if (!tiles.empty()) memcpy(p.htab.data() + 3 * R, tiles.data(), tiles.size() * sizeof(BpTile));
+  memcpy(p.htab.data() + 3 * R + 4 * tiles.size(), gsrc.data(), (size_t)n * sizeof(int));
+}
+
+// The plan's tables onto the device (b->ptab, grown when too small).
+static int bp_upload(l2_ctx* c, const BpPlan& p) {
+  BatchState* b = c->bt;
+  const size_t need = p.htab.size();
   if (need > b->ptab_cap) {
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipStreamSynchronize(c->stream));
     if (b->ptab) { HIPCHK(hipFree(b->ptab)); b->ptab = nullptr; b->ptab_cap = 0; }
     HIPCHK(hipMalloc(&b->ptab, need * sizeof(int)));
     b->ptab_cap = need;
   }
+  HIPCHK(hipMemcpyAsync(b->ptab, p.htab.data(), need * sizeof(int), hipMemcpyHostToDevice, c->stream));      // (htab lives past the caller's synchronise)
+  return L2_OK;
+}
+
+// Enqueue the launch sequences of n checked runs given in packing order (R rows in all).  The first nd runs are decode rows (one row
+// each, l2_step_batch; 0 for l2_seq_prefill_batch): they lie in the first launch sequence, are cut into no tile, and take the decode
+// attention form per (head, row) -- bt_attn_tile_kernel, at any head size and position -- while the tiles of the longer runs take
+// bp_attn_mfma_kernel with its LDS sized by the longest of them.  `logits`: gather every run's last row, final norm and classifier ->
+// b->logits rows 0 .. n-1.  `p` receives the plan, whose htab holds the uploaded tables: the caller keeps it until the stream has been
+// synchronised.  `score` (l2_seq_score_batch): after each launch sequence's layers, the final norm and the classifier of EVERY row of it
+// (bt_classify: the last-row classifier's arithmetic) into b->slogits, then lp_rows_kernel over them with the targets and outputs of
+// `score` at the launch sequence's first row -- all before the next launch sequence overwrites the rows.
+static int bp_enqueue(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0, size_t R, int nd,
+                      bool logits, BpPlan& p, const LpDev* score = nullptr, int top_k = 0) {
+  BatchState* b = c->bt;
+  hipStream_t st = c->stream;
+  const PfActs& P = b->pact;
+  int rc = pf_acts_ensure(c, b->pact);
+  if (rc) return rc;
+  bp_plan(p, pf3_ok(c) ? (int)BP_ROWS : (int)PF_T, n, seqs, n_tokens, tokens, pos0, R, nd);
+  rc = bp_upload(c, p);
+  if (rc) return rc;
   const int* dseq = b->ptab;
   const int* dpos = b->ptab + R;
   const int* dtok = b->ptab + 2 * R;
   const BpTile* dtiles = reinterpret_cast<const BpTile*>(b->ptab + 3 * R);
-  const int* dgsrc = b->ptab + 3 * R + 4 * tiles.size();
-  HIPCHK(hipMemcpyAsync(b->ptab, htab.data(), need * sizeof(int), hipMemcpyHostToDevice, st));      // (htab lives past the caller's synchronise)
-
-  // ---- the launch sequences: prefill_chunk's, over the packed rows
-  for (int k = 0; k < nl; ++k) {
-    const int r0 = k * step, m = (int)std::min<size_t>(step, R - r0), nti = tile0[k + 1] - tile0[k];
+  const int* dgsrc = b->ptab + 3 * R + 4 * p.n_tiles;
+  for (int k = 0; k < p.nl; ++k) {
+    const int r0 = k * p.step, m = (int)std::min<size_t>(p.step, R - r0), nti = p.tile0[k + 1] - p.tile0[k];
     const int ndk = k == 0 ? nd : 0;                           // decode rows of this launch sequence (its rows 0 .. ndk-1)
-    const int chunks = (m + PF_T - 1) / PF_T;
-    const int tt = (m > 32) ? 4 : (m > 16) ? 2 : 1, nt = (chunks > 1) ? chunks * PF_T : 16 * tt;   // token rows the kernels see
-    hipLaunchKernelGGL(pf_embed_kernel, dim3(nt), dim3(256), 0, st, b->px, c->w[L2_T_TOKEN_EMBEDDING], dtok + r0, c->d, m);
-    LCHK(hipGetLastError());
-    const size_t alds = pf_attn_lds(maxp[k] + 15);      // the longest tile's keys
-    const bool mfma_attn = c->pf_attn && !c->opt_exact && (c->hs == 64 || c->hs == 128) && alds <= 150 * 1024;
-    for (int l = 0; l < c->L; ++l) {
-      const size_t loff = (size_t)l * c->S * c->d;
-      PfArgs a;
-      memset(&a, 0, sizeof(a));
-      a.fr = c->w[L2_T_FREQ_REAL]; a.fi = c->w[L2_T_FREQ_IMAG]; a.head_size = c->hs; a.dim = c->d; a.pos0 = 0; a.nvalid = m;
-      a.x = b->px;
-      a.row_seq = dseq + r0; a.row_pos = dpos + r0; a.seq_kc = b->d_kc; a.seq_vc = b->d_vc; a.seq_loff = loff;
-      // rmsnorm + q,k,v + RoPE + every row's cache row at its own (sequence, position) (llama2.ts:216-240)
-      hipLaunchKernelGGL(pf_norm_kernel, dim3(nt), dim3(256), 0, st, b->pxn, b->px, c->w[L2_T_RMS_ATT] + d * l, c->d);
-      pf_weights<MODE_QKV>(c, l, a, L2_T_WQ, L2_T_WK, L2_T_WV);
-      a.xin = b->pxn; a.out = b->pq; a.n = c->d; a.rows = 3 * c->d;
-      launch_pf_gemm<MODE_QKV_ROWS>(c, a, 4, tt, chunks, st);
-      LCHK(hipGetLastError());
-      // attention (llama2.ts:244-267): 16-query tiles on the fp64 MFMA (decode rows: per (head, row)), or the decode form per (head, row)
-      // for every row where prefill_chunk takes it
-      if (mfma_attn) {
-        if (ndk > 0) {
-          AttnArgs aa;
-          fill_attn_args(c, l, aa);      // (the kernel runs one workgroup per (head, row), one split)
-          aa.q = b->pq; aa.xb = b->pxb; aa.att = nullptr; aa.tokpos = nullptr; aa.part = nullptr; aa.counter = nullptr;
-          const AttnRows ar = {dseq + r0, dpos + r0, b->d_kc, b->d_vc, loff};
-          LCHK(launch_bt_attn(c, aa, ar, ndk, st));
-        }
-        if (nti > 0) {
-          BpAttnArgs pa;
-          pa.q = b->pq; pa.xb = b->pxb; pa.seq_kc = b->d_kc; pa.seq_vc = b->d_vc; pa.seq_loff = loff; pa.tiles = dtiles + tile0[k];
-          pa.dim = c->d; pa.seq_len = c->S; pa.inv_sqrt_hs = 1.0 / sqrt((double)c->hs);
-          const dim3 grid(c->H, nti);
-          if (c->hs == 128) {
-            LCHK(lds_opt_in(&bp_attn_mfma_kernel<128>, alds));
-            hipLaunchKernelGGL((bp_attn_mfma_kernel<128>), grid, dim3(256), alds, st, pa);
-          } else {
-            LCHK(lds_opt_in(&bp_attn_mfma_kernel<64>, alds));
-            hipLaunchKernelGGL((bp_attn_mfma_kernel<64>), grid, dim3(256), alds, st, pa);
-          }
-          LCHK(hipGetLastError());
-        }
-      } else {
-        AttnArgs aa;
-        fill_attn_args(c, l, aa);      // (the kernel runs one workgroup per (head, row), one split)
-        aa.q = b->pq; aa.xb = b->pxb; aa.att = nullptr; aa.tokpos = nullptr; aa.part = nullptr; aa.counter = nullptr;
-        const AttnRows ar = {dseq + r0, dpos + r0, b->d_kc, b->d_vc, loff};
-        LCHK(launch_bt_attn(c, aa, ar, m, st));
-      }
-      // wo + residual (llama2.ts:270-273)
-      pf_weights<MODE_WO>(c, l, a, L2_T_WO, -1, -1); a.xin = b->pxb; a.n = c->d; a.rows = c->d;
-      launch_pf_gemm<MODE_WO>(c, a, 4, tt, chunks, st);
-      // rmsnorm + w1,w3 + SwiGLU (llama2.ts:276-289)
-      hipLaunchKernelGGL(pf_norm_kernel, dim3(nt), dim3(256), 0, st, b->pxn, b->px, c->w[L2_T_RMS_FFN] + d * l, c->d);
-      pf_weights<MODE_W13>(c, l, a, L2_T_W1, L2_T_W3, -1);
-      a.xin = b->pxn; a.out = b->phb; a.n = c->d; a.rows = c->h;
-      launch_pf_gemm<MODE_W13>(c, a, 4, tt, chunks, st);
-      // w2 + residual (llama2.ts:292-295)
-      pf_weights<MODE_W2>(c, l, a, L2_T_W2, -1, -1); a.xin = b->phb; a.n = c->h; a.rows = c->d;
-      launch_pf_gemm<MODE_W2>(c, a, 4, tt, chunks, st);
-      LCHK(hipGetLastError());
-    }
-    if (score) {      // every row of this launch sequence: final rmsnorm, classifier (llama2.ts:299-302), log-probabilities
-      hipLaunchKernelGGL(pf_norm_kernel, dim3(nt), dim3(256), 0, st, b->pxn, (const float*)b->px, c->w[L2_T_RMS_FINAL], c->d);
-      for (int s0 = 0; s0 < m; s0 += PF_T) {
-        const int ms = std::min(m - s0, (int)PF_T);
-        PfArgs a;
-        memset(&a, 0, sizeof(a));
-        bt_cls_weights(c, a);
-        a.xin = b->pxn + (size_t)s0 * d; a.out = b->slogits + (size_t)s0 * c->V; a.n = c->d; a.rows = c->V; a.dim = c->d; a.nvalid = ms;
-        bt_gemm<MODE_CLS_ROWS>(c, a, (ms > 32) ? 4 : (ms > 16) ? 2 : 1, st);
-      }
-      LCHK(hipGetLastError());
+    const size_t alds = pf_attn_lds(p.maxp[k] + 15);      // the longest tile's keys
+    const bool mfma = attn_mfma_ok(c, alds);
+    const AttnRows rows = {dseq + r0, dpos + r0, b->d_kc, b->d_vc, 0};
+    // attention: 16-query tiles on the fp64 MFMA (decode rows: per (head, row)), or the decode form per (head, row) for every row where
+    // prefill_chunk takes it
+    const auto attn = [&](int l, size_t loff) -> int {
+      const int nrow = mfma ? ndk : m;
+      if (nrow > 0) { const int e = bt_attn_rows(c, l, P, rows, loff, nrow, st); if (e) return e; }
+      if (!mfma || nti == 0) return L2_OK;
+      BpAttnArgs pa;
+      pa.q = P.q; pa.xb = P.xb; pa.seq_kc = b->d_kc; pa.seq_vc = b->d_vc; pa.seq_loff = loff; pa.tiles = dtiles + p.tile0[k];
+      pa.dim = c->d; pa.seq_len = c->S; pa.inv_sqrt_hs = 1.0 / sqrt((double)c->hs);
+      return launch_attn_mfma(c, bp_attn_mfma_kernel<64>, bp_attn_mfma_kernel<128>, dim3(c->H, nti), alds, pa, st);
+    };
+    rc = pf_layers<PF_GEMM_PROMPT>(c, P, dtok + r0, m, rows, attn, st);
+    if (rc) return rc;
+    if (score) {      // every row of this launch sequence: final rmsnorm, classifier, log-probabilities
+      rc = bt_classify(c, P.x, P.xn, b->slogits, pf_tiles(m).nt, m, st);
+      if (rc) return rc;
       LCHK(launch_lp_rows(c, b->slogits, m, score->target + r0, *score, (size_t)r0, top_k, st));
     }
-    // the residual rows of the runs that end here, into b->x rows seq_a .. seq_b - 1 (pf_embed_kernel as a row gather)
-    if (logits && seq_b[k] > seq_a[k]) {
-      hipLaunchKernelGGL(pf_embed_kernel, dim3(seq_b[k] - seq_a[k]), dim3(256), 0, st, b->x + (size_t)seq_a[k] * d, (const float*)b->px, dgsrc + seq_a[k],
-                         c->d, seq_b[k] - seq_a[k]);
+    // the residual rows of the runs that end here, into b->act.x rows seq_a .. seq_b - 1 (pf_embed_kernel as a row gather)
+    if (logits && p.seq_b[k] > p.seq_a[k]) {
+      hipLaunchKernelGGL(pf_embed_kernel, dim3(p.seq_b[k] - p.seq_a[k]), dim3(256), 0, st, b->act.x + (size_t)p.seq_a[k] * c->d, (const float*)P.x, dgsrc + p.seq_a[k],
+                         c->d, p.seq_b[k] - p.seq_a[k]);
       LCHK(hipGetLastError());
     }
   }
-  if (logits) {      // final rmsnorm + classifier of every run's last row (llama2.ts:299-302)
-    hipLaunchKernelGGL(pf_norm_kernel, dim3(n), dim3(256), 0, st, b->xn, (const float*)b->x, c->w[L2_T_RMS_FINAL], c->d);
-    PfArgs a;
-    memset(&a, 0, sizeof(a));
-    bt_cls_weights(c, a);
-    a.xin = b->xn; a.out = b->logits; a.n = c->d; a.rows = c->V; a.dim = c->d; a.nvalid = n;
-    bt_gemm<MODE_CLS_ROWS>(c, a, (n > 32) ? 4 : (n > 16) ? 2 : 1, st);
-    LCHK(hipGetLastError());
-  }
-  return L2_OK;
+  // final rmsnorm + classifier of every run's last row
+  return logits ? bt_classify(c, b->act.x, b->act.xn, b->logits, n, n, st) : L2_OK;
 }
 
 // Each named sequence's next position as l2_seq_prefill leaves it (after the stream has been synchronised).
 static void bp_set_next(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* pos0) {
   for (int i = 0; i < n; ++i) {
-    const int s = seqs[i], end = pos0[i] + n_tokens[i], next = s == 0 ? c->next_pos : c->bt->next_pos[s];
-    if (end > next || pos0[i] == 0) bt_set_next(c, s, end);
+    const int s = seqs[i], end = pos0[i] + n_tokens[i];
+    if (end > bt_next(c, s) || pos0[i] == 0) bt_set_next(c, s, end);
   }
 }
 
@@ -661,8 +622,8 @@ extern "C" int l2_seq_prefill_batch(l2_ctx* c, int n, const int32_t* seqs, const
   rc = ensure_ready(c);
   if (rc) return rc;
   HIPCHK(hipSetDevice(c->device));
-  std::vector<int> htab;
-  rc = bp_enqueue(c, n, seqs, n_tokens, tokens, pos0, R, 0, logits_out != nullptr, htab);
+  BpPlan plan;
+  rc = bp_enqueue(c, n, seqs, n_tokens, tokens, pos0, R, 0, logits_out != nullptr, plan);
   if (rc) return rc;
   if (logits_out) HIPCHK(hipMemcpyAsync(logits_out, c->bt->logits, (size_t)n * c->V * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -694,8 +655,8 @@ extern "C" int l2_seq_score_batch(l2_ctx* c, int n, const int32_t* seqs, const i
   rc = lp_bufs(c, R, top_k, o);
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(o.target, targets, R * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  std::vector<int> htab;
-  rc = bp_enqueue(c, n, seqs, n_tokens, tokens, pos0, R, 0, false, htab, &o, top_k);
+  BpPlan plan;
+  rc = bp_enqueue(c, n, seqs, n_tokens, tokens, pos0, R, 0, false, plan, &o, top_k);
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(lp_out, o.lp, R * sizeof(double), hipMemcpyDeviceToHost, st));
   if (argmax_out) HIPCHK(hipMemcpyAsync(argmax_out, o.amax, R * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -724,11 +685,8 @@ static int bt_step(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_token
   const int given = (temperature != nullptr) + (topp != nullptr) + (rng_state != nullptr);
   if (given != 0 && given != 3) return fail(L2_E_ARG, "temperature / topp / rng_state: give all three, or none for every row greedy");
   bool any = false;
-  for (int i = 0; given && i < n; ++i) {
-    if (!(temperature[i] == temperature[i]) || !(topp[i] == topp[i])) return fail(L2_E_ARG, "row %d: temperature / topp is NaN", i);
-    if (temperature[i] != 0.0) any = true;
-  }
-  if (any && c->V > l2s::MAX_VOCAB) return fail(L2_E_CONFIG, "device sampler supports vocabularies up to %d", (int)l2s::MAX_VOCAB);
+  rc = bt_check_sampling(c, n, temperature, topp, &any);
+  if (rc) return rc;
   if (top_k > c->V) return fail(L2_E_ARG, "top_k %d > vocab_size %d", top_k, c->V);
 
   // packing order: decode rows (runs of one row) first, then the longer runs, each group in call order
@@ -764,24 +722,13 @@ static int bt_step(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_token
     if (rc) return rc;
   }
   HIPCHK(hipStreamSynchronize(st));      // (the pinned tables: the previous call's copies have completed)
-  std::vector<int> htab;
-  rc = bp_enqueue(c, n, ps.data(), pn.data(), ptok.data(), pp.data(), R, nd, true, htab);
+  BpPlan plan;
+  rc = bp_enqueue(c, n, ps.data(), pn.data(), ptok.data(), pp.data(), R, nd, true, plan);
   if (rc) return rc;
   HIPCHK(hipMemsetAsync(b->tab, 0, 4 * BT_MAX * sizeof(int), st));
-  if (any) {
-    l2s::BatchSampler& sm = *b->smp;
-    for (int j = 0; j < n; ++j) { sm.h_params[2 * j] = temperature[ord[j]]; sm.h_params[2 * j + 1] = topp[ord[j]]; sm.h_rng[j] = rng_state[ord[j]]; }
-    HIPCHK(l2s::reset_rows(sm, n, st));
-    HIPCHK(hipMemcpyAsync(sm.params, sm.h_params, 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sm.rng, sm.h_rng, (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-    LCHK(l2s::enqueue_rows(sm, b->logits, n, st));
-    hipLaunchKernelGGL(bt_pick_kernel, dim3(n), dim3(1024), 0, st, (const float*)b->logits, c->V, (const double*)sm.params, sm.pick,
-                       b->tok_of(), b->pos_of(), (const int*)b->start_of(), b->out, c->S);
-  } else {
-    hipLaunchKernelGGL(bt_argmax_kernel, dim3(n), dim3(1024), 0, st, (const float*)b->logits, c->V, b->tok_of(), b->pos_of(), (const int*)b->start_of(),
-                       b->out, c->S);
-  }
-  LCHK(hipGetLastError());
+  if (any) { rc = bt_sampler_upload(*b->smp, n, {temperature, topp, rng_state}, ord.data(), st); if (rc) return rc; }
+  rc = bt_enqueue_pick(c, n, any, st);
+  if (rc) return rc;
   std::vector<char> lpbytes;
   if (pick_lp_out) {      // after the pick: its log-probability under the unscaled logits, and the top-k
     LCHK(launch_lp_rows(c, b->logits, n, b->tok_of(), o, 0, top_k, st));
@@ -796,10 +743,7 @@ static int bt_step(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_token
     if (!identity) { lg.resize((size_t)n * c->V); dst = lg.data(); }
     HIPCHK(hipMemcpyAsync(dst, b->logits, (size_t)n * c->V * sizeof(float), hipMemcpyDeviceToHost, st));
   }
-  if (any) {
-    HIPCHK(hipMemcpyAsync(b->smp->h_rng, b->smp->rng, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(b->smp->h_stats, b->smp->stats, 2 * (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  }
+  if (any) { rc = bt_sampler_fetch(*b->smp, n, st); if (rc) return rc; }
   HIPCHK(hipStreamSynchronize(st));
   for (int j = 0; j < n; ++j) {
     const int i = ord[j];
@@ -812,11 +756,8 @@ static int bt_step(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_token
       pick_lp_out[i] = plp[j];
       for (int q = 0; q < top_k; ++q) { top_ids_out[(size_t)i * top_k + q] = tid[(size_t)j * top_k + q]; top_lp_out[(size_t)i * top_k + q] = tlp[(size_t)j * top_k + q]; }
     }
-    if (any) {
-      rng_state[i] = b->smp->h_rng[j];
-      for (int k = 0; k < 2; ++k) { const unsigned long long v = b->smp_stats[k] + b->smp->h_stats[2 * j + k]; b->smp_stats[k] = v < b->smp_stats[k] ? ~0ull : v; }
-    }
   }
+  if (any) bt_sampler_finish(b, n, rng_state, ord.data());
   bp_set_next(c, n, seqs, n_tokens, pos0);
   return L2_OK;
 }
@@ -876,7 +817,7 @@ extern "C" int l2_seq_fork(l2_ctx* c, int src, int n_dst, const int32_t* dsts, i
     seen[s] = true;
     a.dst4[i >> 2] |= (unsigned)s << (8 * (i & 3));
   }
-  const int have = src == 0 ? c->next_pos : b->next_pos[src];
+  const int have = bt_next(c, src);
   if (c->opt_pos_check && n_pos > have)
     return fail(L2_E_STATE, "L2_CHECK_POS: n_pos %d rows of sequence %d were asked for, cache rows 0 .. %d have been written", n_pos, src, have - 1);
   HIPCHK(hipSetDevice(c->device));

@@ -119,6 +119,10 @@ struct P2PArgs {
 
 // ------------------------------------------------------------------------------------------------
 struct BatchState;                   // batched decode of independent sequences (batch_host.hip.h)
+// The activations of one prompt / batch launch sequence (prefill_host.hip.h: pf_layers): [rows][d | max(d, h) | d | d | h].  Three sets exist:
+// the context's (l2_prefill, l2_seq_prefill), and the batch step's BT_MAX rows and the packed path's (batch_host.hip.h: BatchState).
+struct PfActs { float *x = nullptr, *xn = nullptr, *q = nullptr, *xb = nullptr, *hb = nullptr; };
+
 struct l2_ctx {
   int32_t hdr[7];
   int d, h, L, H, V, S, hs;
@@ -193,7 +197,7 @@ struct l2_ctx {
   size_t probe_used = 0;
   bool probe_on = false;
   // prefill (prefill.hip.h): 16-token chunk buffers
-  float *pf_x = nullptr, *pf_xn = nullptr, *pf_q = nullptr, *pf_xb = nullptr, *pf_hb = nullptr;
+  PfActs pf;                        // (allocated at the first launch sequence: prefill_host.hip.h, pf_acts_ensure)
   int* pf_tok = nullptr;
   int* tokpos = nullptr;    // device {token,pos,step,0}
   int* h_tokpos = nullptr;  // pinned

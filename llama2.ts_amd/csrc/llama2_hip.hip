@@ -25,6 +25,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <algorithm>
 #include <vector>
 
@@ -127,7 +128,7 @@ extern "C" void l2_destroy(l2_ctx* c) {
   if (c->gran_ep) hipFree(c->gran_ep);
   if (c->h_herr) hipHostFree(c->h_herr);
   for (hipEvent_t e : c->probe) hipEventDestroy(e);
-  { float* pb[] = {c->pf_x, c->pf_xn, c->pf_q, c->pf_xb, c->pf_hb}; for (float* b : pb) if (b) hipFree(b); if (c->pf_tok) hipFree(c->pf_tok); }
+  { float* pb[] = {c->pf.x, c->pf.xn, c->pf.q, c->pf.xb, c->pf.hb}; for (float* b : pb) if (b) hipFree(b); if (c->pf_tok) hipFree(c->pf_tok); }
   if (c->pollute_sink) hipFree(c->pollute_sink);
   if (c->tokpos) hipFree(c->tokpos);
   if (c->d_tokens) hipFree(c->d_tokens);
