@@ -103,7 +103,8 @@ enum {
                                  Applies per sequence to the batch calls below (sequence 0 shares its position with l2_forward / l2_prefill) */
   L2_OPT_SEQS = 11,           /* read-only: sequences reserved by l2_seq_reserve (0 before it) */
   L2_OPT_BATCH_SAMPLED_TOKENS = 12, /* read-only: tokens l2_decode_sample_batch and l2_step_batch have sampled (temperature != 0), saturating */
-  L2_OPT_BATCH_SAMPLED_SERIAL = 13  /* read-only: of those, the ones the margin form's serial loop picked */
+  L2_OPT_BATCH_SAMPLED_SERIAL = 13, /* read-only: of those, the ones the margin form's serial loop picked */
+  L2_OPT_ATTN_WO_STREAM = 14  /* read-only: 1 when a step of the last forward / decode call ran attention and wo as ONE launch (one GPU, streaming form) */
 };
 
 typedef struct l2_ctx l2_ctx;

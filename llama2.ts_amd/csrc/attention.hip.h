@@ -48,6 +48,9 @@ struct AttnArgs {
   // workgroups of the same launch; tag = *gout_ep + 1 (advanced by the launch after this one: tp_p2p_combine_kernel)
   unsigned long long* gout;
   const unsigned* gout_ep;
+  // ... or, on one GPU (attn_wo_stream_kernel: no launch behind it advances a counter), a tag the kernel makes from {run nonce, pos, layer}
+  // (attn_wo_stream_tag); 0 = take it from gout_ep
+  unsigned gout_tag;
   unsigned long long* dbg;  // diagnostic stamps (L2_STAMPS builds), else null
 };
 
@@ -185,7 +188,7 @@ __device__ __forceinline__ void attn_tile_body(const AttnArgs& a, char* smem, co
   const double q0 = cl ? (double)q4.x : 0.0, q1 = cl ? (double)q4.y : 0.0, q2 = cl ? (double)q4.z : 0.0, q3 = cl ? (double)q4.w : 0.0;
   const double rsq = a.inv_sqrt_hs;             // 1 / sqrt(head_size), rounded once by the host (llama2.ts:253 divides)
   // (requested here, used at the very end: the launch counter the output granules' tag comes from)
-  const unsigned otag = a.gout ? __hip_atomic_load(a.gout_ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u : 0u;
+  const unsigned otag = a.gout ? (a.gout_tag ? a.gout_tag : __hip_atomic_load(a.gout_ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u) : 0u;
   double* Pw = P + (size_t)wave * NT * ATT_PS;
   STAMP(1);
 
@@ -464,6 +467,123 @@ __global__ void __launch_bounds__(512) attn_wo_kernel(const AttnArgs at, const P
   while (h >= at.n_heads) { h -= at.n_heads; ++sp; }
   const int pos = at.tokpos[1];
   attn_tile_dispatch<LR, NW, NT>(at, smem, h, sp, pos);
+}
+
+// ------------------------------------------------------------------------------------------------
+// ONE launch for attention and the STREAMING-form wo GEMV on one GPU (Llama-2-7B: llama2.ts:244-267 -> 270-273).  wo's weights depend on
+// nothing the attention computes, and a wave's whole share of them (2 rows x n columns: 32 KB at n = 4096, 128 VGPRs) fits its registers
+// when a CU holds one ten-wave workgroup (AWOS_WAVES below).  So a wo wave requests ALL of its weights the moment it starts; the attention of the same
+// launch (the first `nattn` workgroups: lowest block ids, dispatched first, they never wait) runs underneath their ~10 us flight and
+// publishes its output as hand-off granules besides xb.  Vector memory returns in order, so the answer to a wo wave's first sweep over the
+// granules arrives behind its own weights: nothing polls while the stream runs, and the hand-off no longer competes with it.
+//   wo role: wave `wave` of workgroup b of the role takes row group b * AWOS_WAVES + wave of the shipped wo launch: the repacked copy
+//   (pack_kernel, U = 2, one round of row groups: [column batch][row group][r][u][lane]) is read where it lies.  Every wave gathers an eighth of the input
+//   vector into LDS (ONE gather per workgroup), one barrier, then the FMAs in exactly the order of phase_body's consume -- column batch,
+//   u, x / y / z / w, into the same acc[r] -- wave_sum2 and finish_group<MODE_WO>: the same bits as the two launches.
+// Tags: no later launch advances a counter on one GPU, so both roles make the tag from what they read anyway: {run nonce, pos * L + layer}
+// (the host bumps the nonce per run and per blocking call: tokpos[3]) -- granule memory only ever holds tags of EARLIER launches.
+__device__ __forceinline__ unsigned attn_wo_stream_tag(int nonce, int pos, int layer, int n_layers) {
+  return 0x80000000u | (((unsigned)nonce & 0x7ffu) << 20) | (((unsigned)pos * (unsigned)n_layers + (unsigned)layer) & 0xfffffu);
+}
+
+// Waves of a workgroup of the fused launch.  TEN, not eight: the attention workgroups keep their CUs for the whole attention, and a wo
+// workgroup that finds no free CU starts -- and requests its weights -- only when one of them ends (seen in the first version: 32 of 256
+// eight-wave wo workgroups started 5 - 10 us late and ended the launch 3 - 5 us after the others).  At three waves per SIMD (<= 168
+// VGPRs) a CU holds ten waves, 2048 row groups are 205 workgroups, and 205 + 32 workgroups are all resident from the start.
+constexpr int AWOS_WAVES = 10;
+
+template <int NCH>
+__device__ __forceinline__ void wo_stream_body(const PhaseArgs& a, char* smem, const int vblock, const unsigned tag, int token, const int pos,
+                                               int* herr, const unsigned long long wait_ticks) {
+  constexpr int R = 2, U = 2;
+  constexpr int CH = NCH * 16;                      // float4 of the input vector a wave gathers: n4 / 8
+  constexpr int NU = (CH + 63) / 64;
+  f4* xs4 = reinterpret_cast<f4*>(smem);            // n4 = NCH * 128 float4
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int groups = (a.rows + R - 1) / R;
+  const int place = vblock * AWOS_WAVES + wave;
+  const bool have = place < groups;
+  const int pl = have ? place : groups - 1;         // (unconditional requests: a wave without a row group re-reads the last one's)
+  // ---- the wave's whole share of the matrix, first thing: [batch ci][place][r][u][lane] float4 (pack_kernel, one round)
+  const f4* base = reinterpret_cast<const f4*>(a.wp) + (size_t)pl * (R * U * 64) + lane;
+  const size_t cstride = (size_t)groups * (R * U * 64);
+  f4 w[NCH][R][U];
+  auto issue = [&](int ci) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int r = 0; r < R; ++r) w[ci][r][u] = __builtin_nontemporal_load(base + cstride * ci + (r * U + u) * 64);
+  };
+#pragma unroll
+  for (int ci = 0; ci < NCH; ++ci) issue(ci);
+  // ---- epilogue operands (residual; layer 0: the token record, and the argmax keys are re-armed -- phase_body, a.emb && a.tok_out)
+  if (a.emb && a.tok_out) {
+    const int step = a.tokpos[2];
+    if (step > 0) token = a.tok_out[step - 1];
+    if (vblock == 0 && tid < 8) a.amax[(size_t)tid * 16] = 0ull;
+  }
+  const EpiPre pre = epi_prefetch<MODE_WO, R>(a, pl, lane, token, pos);
+  // ---- the input vector: granules of the attention workgroups of this launch, past L1; the data is its own flag.  Eight waves gather an
+  // eighth each (the others only carry weights).  Vector memory returns in order: the first sweep's answer arrives behind the wave's own
+  // weights, so nothing polls while the stream runs.  (Requesting the first sweep behind three quarters of the weights, so that the FMAs
+  // of the batches that have landed run under the rest of the stream, was measured: 167 VGPRs and no faster.)
+  if (wave < 8) {
+    f4 xr[NU];
+    granules_gather_f4<NU>(a.gran + (size_t)wave * (CH * 4), CH * 4, lane, tag, xr, herr, wait_ticks, 1, const_cast<unsigned*>(a.gran_ep) + 1);
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+      if (u * 64 + lane < CH) xs4[wave * CH + u * 64 + lane] = xr[u];
+  }
+#ifdef L2_STAMPS
+  // diagnostic build: when this workgroup's first wave had its weights AND its eighth of the input vector (100 MHz clock all XCDs share)
+  if (a.dbg_wg && tid == 0 && blockIdx.x < 1024) { unsigned long long t; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)); a.dbg_wg[2048 + 2 * blockIdx.x] = t; }
+#endif
+  __syncthreads();
+  double acc[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) acc[r] = 0.0;
+#pragma unroll
+  for (int ci = 0; ci < NCH; ++ci) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const f4 xv = xs4[ci * (64 * U) + u * 64 + lane];
+      const double x0 = xv.x, x1 = xv.y, x2 = xv.z, x3 = xv.w;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        acc[r] += (double)w[ci][r][u].x * x0;
+        acc[r] += (double)w[ci][r][u].y * x1;
+        acc[r] += (double)w[ci][r][u].z * x2;
+        acc[r] += (double)w[ci][r][u].w * x3;
+      }
+    }
+  }
+  wave_sum2(acc[0], acc[R - 1]);
+  unsigned long long nobest = 0;
+  if (have) finish_group<MODE_WO, R, true>(a, place, acc, lane, token, pos, pre, nobest);
+}
+
+// NCH = column batches of a row (n = NCH * 512 floats: 1024, 2048, 4096); heads of 128 floats (the eight-wave tile kernel)
+template <int NCH>
+__global__ void __launch_bounds__(64 * AWOS_WAVES) attn_wo_stream_kernel(const AttnArgs at, const PhaseArgs wo, const int nattn, const int layer, const int n_layers) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  // every kernel argument either role needs in ONE fetch round before the role branch (see qkv_attn_small_kernel)
+#define L2_PIN4(x0, x1, x2, x3) asm volatile("" ::"s"(x0), "s"(x1), "s"(x2), "s"(x3))
+  L2_PIN4(wo.wp, wo.tokpos, wo.emb, wo.res.addr()); L2_PIN4(wo.out.addr(), wo.aux.addr(), wo.gran, wo.gran_ep); L2_PIN4(wo.rows, wo.dim, wo.tok_out, wo.amax);
+  L2_PIN4(wo.partial, wo.push, wo.gin_herr, nattn); L2_PIN4(at.q.addr(), at.kc.addr(), at.vc.addr(), at.att.addr()); L2_PIN4(at.xb.addr(), at.tokpos, at.gout, at.dim);
+  L2_PIN4(at.head_size, at.seq_len, at.n_heads, at.nsplit); L2_PIN4(at.kv_dim, at.kv_mul, at.inv_sqrt_hs, at.exact); L2_PIN4(at.wait_ticks, layer, n_layers, at.dbg);
+#undef L2_PIN4
+#ifdef L2_STAMPS
+  Stamps st_(nullptr, wo.dbg_wg);      // every workgroup of either role: {start, end}
+#endif
+  const int token = wo.tokpos[0], pos = wo.tokpos[1], nonce = wo.tokpos[3];
+  const unsigned tag = attn_wo_stream_tag(nonce, pos, layer, n_layers);
+  if ((int)blockIdx.x >= nattn) { wo_stream_body<NCH>(wo, smem, (int)blockIdx.x - nattn, tag, token, pos, wo.gin_herr, at.wait_ticks); return; }
+  if ((int)threadIdx.x >= 512) return;                               // (the eight-wave attention form in a ten-wave launch)
+  int sp = 0, h = (int)blockIdx.x;
+  while (h >= at.n_heads) { h -= at.n_heads; ++sp; }
+  AttnArgs b = at;
+  b.gout_tag = tag;
+  attn_tile_dispatch<32, 8, 8>(b, smem, h, sp, pos);
 }
 
 template <int LR, int NW, int NT>

@@ -152,9 +152,13 @@ struct l2_ctx {
   std::vector<void*> p2p_opened;     // IPC mappings to close
   bool p2p_peers_ready = false;
   // fused attention + wo launch of a tensor-parallel rank (attention.hip.h: attn_wo_kernel)
-  unsigned long long* awo_gran = nullptr;   // [d / G] hand-off granules: the attention output of this rank's heads
-  unsigned* awo_ep = nullptr;               // its launch counter (advanced by the combine launch that follows)
+  unsigned long long* awo_gran = nullptr;   // [d / G] hand-off granules: the attention output of this rank's heads (one GPU: of all heads)
+  unsigned* awo_ep = nullptr;               // its launch counter (advanced by the combine launch that follows; unused on one GPU), then the "a wait gave up" word
   int opt_awo = 1;                          // L2_TP_ATTN_WO=0: attention and wo as two launches (A/B, development switch)
+  int opt_awo_stream = 1;                   // L2_ATTN_WO_STREAM=0: one GPU, streaming-form wo: attention and wo as two launches
+  bool cur_awo_stream = false;              // the step being enqueued / captured is of the level that takes that launch (set_level)
+  bool last_awo_stream = false;             // a step of the last forward / decode call took it (L2_OPT_ATTN_WO_STREAM)
+  unsigned run_nonce = 0;                   // tokpos[3]: a number per run / blocking call, so that no two fused launches in a row share a hand-off tag
   TpPush* tp_push = nullptr;         // device table of the peers' granule inboxes for the GEMV epilogues (kernels.hip.h: tp_push_row)
   int opt_push = 1;                  // L2_TP_PUSH=0: partials through c->partial and the flag exchange (round-4 form; A/B, development switch)
   bool rccl_graph = false;           // the RCCL collectives of the step are captured into the per-token hipGraph (cleared if capture is refused)

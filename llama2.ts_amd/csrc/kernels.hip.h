@@ -183,7 +183,9 @@ struct PhaseArgs {
   unsigned long long* dbg_wg;  // lines -- a fifth cost every launch of the small models ~0.1 us, 2 % of a stories110M token)
 #endif
 };
+#ifndef L2_STAMPS      // (the diagnostic build carries two more pointers)
 static_assert(sizeof(void*) != 8 || sizeof(PhaseArgs) <= 224 + 16, "PhaseArgs: keep the kernel-argument block within four 64-byte lines");
+#endif
 
 // Tensor-parallel push (tp_exchange.hip.h): where the fp64 partial of a row goes.  gin[r] = rank r's inbox of granule pairs,
 // [2 parities][MAXG sources][n] x 16 bytes, mapped into this process (uncached memory); in a shard-timing context every "peer" is this rank.

@@ -125,7 +125,7 @@ static void pollute_behind(const l2_ctx* c, hipStream_t st) {
   add(c->hb, (size_t)c->h_loc * 4); add(c->hb2, (size_t)c->h_loc * 4); add(c->q, (size_t)c->d_loc * 4); add(c->k, (size_t)c->kvd_loc * 4); add(c->v, (size_t)c->kvd_loc * 4);
   add(c->logits_loc, (size_t)c->V_loc * 4); add(c->amax, 8 * 16 * 8); add(c->attn_counter, (size_t)c->H_loc * CTR_STRIDE * 4);
   add(c->attn_part, (size_t)c->H_loc * 8 * (((size_t)c->hs + 2 + 15) & ~(size_t)15) * 8); add(c->gran, ((size_t)c->d_loc + 2 * (size_t)c->kvd_loc) * 8);
-  add(c->gran_ep, (size_t)c->H_loc * 4 + 16); add(c->tokpos, 16); add(c->d_tokens, (size_t)c->S * 4); add(c->att, (size_t)c->H_loc * c->S * 4);
+  add(c->gran_ep, (size_t)c->H_loc * 4 + 16); add(c->awo_gran, (size_t)c->d_loc * 8); add(c->tokpos, 16); add(c->d_tokens, (size_t)c->S * 4); add(c->att, (size_t)c->H_loc * c->S * 4);
   p.nb = nb; p.kc = c->kc; p.vc = c->vc; p.tokpos = c->tokpos; p.sink = c->pollute_sink; p.L = c->L; p.S = c->S; p.kvd = c->kvd_loc;
   l2_launch_one(c, l1_pollute_kernel, dim3(c->n_cus * 4), dim3(256), 0, st, p);      // four workgroups per CU: every CU gets some
 }
@@ -397,5 +397,51 @@ static hipError_t launch_attn_wo(const l2_ctx* c, int l, const PhaseArgs& wo_in,
                          l2_launch(c, attn_wo_kernel<XVV, 2, 32, 8, 8>, grid, block, lds, st, at, wo, nattn); } while (0)
   if (xv == 2) L2_AWO(2); else if (xv == 4) L2_AWO(4); else L2_AWO(8);
 #undef L2_AWO
+  return hipGetLastError();
+}
+
+// ---- the fused attention + wo launch on ONE GPU under the streaming form (attention.hip.h: attn_wo_stream_kernel) ------------------
+// Taken when wo is the streaming form read from a valid repacked copy (U = 2) whose waves have ONE row group each (the copy is then
+// [column batch][row group][r][u][lane] whatever the workgroup size it was packed for: place = row group), heads are
+// 128 wide (the eight-wave tile kernel), a row has 2, 4 or 8 column batches (d = 1024, 2048, 4096: a wave's whole share of the matrix
+// fits its registers), one GPU, the reference's own value accumulate is not asked for and no split count is forced.  Whatever the
+// position: split_level gives such a context the level "fused, one workgroup per head".  L2_ATTN_WO_STREAM=0 keeps the two launches.
+static bool attn_wo_stream_shape_ok(const l2_ctx* c) {
+  if (!c->opt_awo_stream || c->tp_path || c->G != 1 || !c->awo_gran || !c->awo_ep || !c->h_herr_dev || !attn_vec(c)) return false;
+  if (c->hs != 128 || c->KVH <= 0 || c->d_loc != c->d || !(c->d == 1024 || c->d == 2048 || c->d == 4096)) return false;
+  if (use_small(c, MODE_WO, c->d, c->d)) return false;
+  const l2_ctx::Packed& p = c->packed[MODE_WO];
+  if (!c->packed_valid || !p.buf || p.U != 2) return false;
+  const Geo g = pick_geo(c, MODE_WO, c->d, c->d, c->d);      // the copy is only good for the geometry it was packed for (launch_phase)
+  if (!(g.vec && g.U == 2 && g.nwaves == p.nwaves && g.grid == p.grid)) return false;
+  const int groups = c->d / 2;
+  if (groups > p.grid * p.nwaves) return false;              // one round of row groups per wave
+  if ((long long)c->S * c->L > 0xfffff) return false;        // pos * L + layer in 20 bits of the tag
+  if (c->H + (groups + AWOS_WAVES - 1) / AWOS_WAVES > c->n_cus) return false;      // every workgroup of both roles resident from the start
+  return (size_t)attn_tile_lds(c->S, 1, 8, 8) <= 160 * 1024;
+}
+static bool attn_wo_stream_ok(const l2_ctx* c) {
+  return c->cur_awo_stream && c->cur_splits == 1 && !c->opt_exact && c->attn_splits_forced <= 0 && attn_wo_stream_shape_ok(c);
+}
+
+static hipError_t launch_attn_wo_stream(const l2_ctx* c, int l, const PhaseArgs& wo_in, hipStream_t st) {
+  AttnArgs at;
+  fill_attn_args(c, l, at);
+  at.gout = c->awo_gran; at.wait_ticks = 200000000ull;      // 2 s
+  PhaseArgs wo = wo_in;
+  wo.gran = c->awo_gran; wo.gran_ep = c->awo_ep; wo.gin_herr = c->h_herr_dev;
+  if (!wo.wp) return hipErrorInvalidValue;
+#ifdef L2_STAMPS
+  wo.dbg_wg = c->dbg + 66 * 108 + (size_t)(g_stamp_slot % 64) * 2048; g_stamp_slot += 2;      // two slots: {start, end} of every workgroup, then the wo role's "input landed"
+  wo.dbg = nullptr;
+#endif
+  const int nattn = c->H * at.nsplit, nch = c->d / 512;
+  const int nwo = (c->d / 2 + AWOS_WAVES - 1) / AWOS_WAVES;   // one row group per wave
+  const size_t lds_a = attn_tile_lds(c->S, at.nsplit, 8, 8), lds_w = (size_t)c->d * 4, lds = lds_a > lds_w ? lds_a : lds_w;
+  const dim3 grid(nattn + nwo), block(64 * AWOS_WAVES);
+#define L2_AWOS(NCH) do { hipError_t e_ = lds_opt_in(&attn_wo_stream_kernel<NCH>, lds); if (e_ != hipSuccess) return e_; \
+                          l2_launch(c, attn_wo_stream_kernel<NCH>, grid, block, lds, st, at, wo, nattn, l, c->L); } while (0)
+  if (nch == 2) L2_AWOS(2); else if (nch == 4) L2_AWOS(4); else L2_AWOS(8);
+#undef L2_AWOS
   return hipGetLastError();
 }

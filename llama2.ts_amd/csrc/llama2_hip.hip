@@ -76,25 +76,39 @@ static void destroy_graphs(l2_ctx* c) {
 // 8 at every position where they beat 1; the crossover is at 140-160 rows for 64- and 128-wide heads alike).
 static const int kSplitLevels[NLEV] = {1, 1, 8};
 static bool fused_shape_ok(const l2_ctx* c);
+static bool attn_wo_stream_shape_ok(const l2_ctx* c);
 // Level of a step by its position.  Where the fused QKV + attention launch applies (launch.hip.h: fused_shape_ok) it takes the
 // middle of the range: its attention workgroups request their cache rows while the GEMV runs, so ONE workgroup per head keeps up
 // to 256 rows (two launches split a head over 8 workgroups from 144), but below `fuse_min_rows` the hand-off costs more than the
 // launch boundary it replaces (stories110M: two launches win by 2-3 % up to 128 rows, the fused launch by 4 % from there to 256;
 // stories15M: the fused launch wins from the first position -- profiles/r04/fused_qkv_attention_ab.txt, last block).
+// Where the fused attention + wo launch of the streaming form applies (launch.hip.h: attn_wo_stream_shape_ok; Llama-2-7B) the middle
+// level is "fused, one workgroup per head": the attention runs underneath wo's weight stream, off the critical path, so a head no longer
+// needs 8 workgroups from 145 rows -- one keeps up to kAwoStreamRows; beyond, the step is the two launches with 8 splits.
+static const int kAwoStreamRows = 256;
 static int split_level(const l2_ctx* c, int pos) {
   if (c->attn_splits_forced > 0 || c->opt_exact) return 0;
   const bool fusable = fused_shape_ok(c);
-  int unsplit_to = (c->split_rows_set || !fusable) ? c->split_rows : 256;
+  const bool awos = !fusable && attn_wo_stream_shape_ok(c);
+  int unsplit_to = c->split_rows_set ? c->split_rows : (fusable ? 256 : (awos ? kAwoStreamRows : c->split_rows));
   if (fusable && unsplit_to > 256) unsplit_to = 256;      // the fused launch's attention role is built for one round of rows (attention.hip.h: attn_tile_dispatch)
   const int rows = pos + 1;
   if (rows > unsplit_to) return 2;
+  if (awos) return 1;
   return (fusable && rows > c->fuse_min_rows) ? 1 : 0;
+}
+// (L2_OPT_ATTN_WO_STREAM) does a step of positions pos0 .. pos0 + steps - 1 take the fused attention + wo launch?
+static void note_awo_stream(l2_ctx* c, int pos0, int steps) {
+  c->last_awo_stream = false;
+  if (!attn_wo_stream_shape_ok(c)) return;
+  for (int s = 0; s < steps && !c->last_awo_stream; ++s) c->last_awo_stream = split_level(c, pos0 + s) == 1;
 }
 static int splits_of(const l2_ctx* c, int level) { return c->attn_splits_forced > 0 ? c->attn_splits_forced : kSplitLevels[level]; }
 // what a step of this level is enqueued with
 static void set_level(l2_ctx* c, int level) {
   c->cur_splits = splits_of(c, level);
   c->cur_fused = level == 1 || (c->opt_fuse_splits && !c->opt_exact && fused_shape_ok(c));      // (the switch: fused wherever the shape allows -- tests)
+  c->cur_awo_stream = level == 1;
 }
 
 extern "C" void l2_destroy(l2_ctx* c) {
@@ -205,6 +219,7 @@ static int create_impl(const int32_t cfg[7], int device, int rank, int G, const 
   c->p2p_fenced = env_int("L2_TP_FENCED", 0) ? 1 : 0;
   c->opt_push = dev_int("L2_TP_PUSH", 1) && !c->p2p_fenced;      // (the fenced form is the flag exchange)
   c->opt_awo = dev_int("L2_TP_ATTN_WO", 1);
+  c->opt_awo_stream = dev_int("L2_ATTN_WO_STREAM", 1);
   { const int ws = env_int("L2_TP_WAIT_S", 30); c->p2p_wait_ticks = (unsigned long long)(ws > 0 ? ws : 30) * 100000000ull; }
 
 #define CK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { int rc_ = fail(L2_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); l2_destroy(c); return rc_; } } while (0)
@@ -236,11 +251,9 @@ static int create_impl(const int32_t cfg[7], int device, int rank, int G, const 
   if (c->tp_path) CK(hipExtMallocWithFlags((void**)&c->logits, (size_t)V * 4, hipDeviceMallocUncached));
   else CK(hipMalloc(&c->logits, (size_t)V * 4));
   if (c->tp_path) { CK(hipMalloc(&c->logits_loc, (size_t)c->V_loc * 4)); CK(hipMalloc(&c->partial, (size_t)d * 8)); }
-  if (c->tp_path) {
-    CK(hipMalloc(&c->awo_gran, (size_t)c->d_loc * 8)); CK(hipMemsetAsync(c->awo_gran, 0, (size_t)c->d_loc * 8, c->stream));
-    CK(hipMalloc(&c->awo_ep, 16)); CK(hipMemsetAsync(c->awo_ep, 0, 16, c->stream));
-  }
-  else c->logits_loc = c->logits;
+  CK(hipMalloc(&c->awo_gran, (size_t)c->d_loc * 8)); CK(hipMemsetAsync(c->awo_gran, 0, (size_t)c->d_loc * 8, c->stream));
+  CK(hipMalloc(&c->awo_ep, 16)); CK(hipMemsetAsync(c->awo_ep, 0, 16, c->stream));
+  if (!c->tp_path) c->logits_loc = c->logits;
   CK(hipMalloc(&c->kc, kv * 4)); CK(hipMalloc(&c->vc, kv * 4));
   CK(hipMemsetAsync(c->kc, 0, kv * 4, c->stream)); CK(hipMemsetAsync(c->vc, 0, kv * 4, c->stream));
   float* zero[] = {c->x, c->xn, c->xb, c->xb2, c->hb, c->hb2, c->q, c->k, c->v};
@@ -666,6 +679,10 @@ static int enqueue_forward_impl(l2_ctx* c, hipStream_t st, bool to_host, int fol
       LCHK(launch_phase<MODE_QKV>(c, a, st));
       if (attn_wo_ok(c)) {
         LCHK(launch_attn_wo(c, l, wo_args(c, l), st));      // attention and the rank's wo shard in ONE launch (attention.hip.h: attn_wo_kernel)
+      } else if (attn_wo_stream_ok(c)) {
+        a = wo_args(c, l);
+        if (l == 0) greedy(a);
+        LCHK(launch_attn_wo_stream(c, l, a, st));           // ... and on one GPU under the streaming form's wo (attn_wo_stream_kernel)
       } else {
         LCHK(launch_attn(c, l, st));
         a = wo_args(c, l);
@@ -927,9 +944,10 @@ extern "C" int l2_forward(l2_ctx* c, int token, int pos, float* logits_out) {
   if (rc) return rc;
   HIPCHK(hipSetDevice(c->device));
   c->next_pos = pos + 1;
-  c->h_tokpos[0] = token; c->h_tokpos[1] = pos; c->h_tokpos[2] = 0; c->h_tokpos[3] = 0;
+  c->h_tokpos[0] = token; c->h_tokpos[1] = pos; c->h_tokpos[2] = 0; c->h_tokpos[3] = (int)(++c->run_nonce & 0x7ffu);
   const int lvl = split_level(c, pos);
   set_level(c, lvl);
+  note_awo_stream(c, pos, 1);
   if (aql_usable(c) && c->opt_zero_copy && !c->tp_path && (c->aql || !aql_open(c)) && !aql_record_level(c, lvl, enqueue_forward_call, &c->aql_step[lvl])) {
     // the library's own queue: {token, pos} read from pinned host memory by the first launch, logits written straight into the
     // host's buffer by the classifier, one doorbell, one signal
@@ -982,7 +1000,8 @@ static int run_greedy(l2_ctx* c, int first_token, int pos0, int steps, bool time
   if (rc) return rc;
   HIPCHK(hipSetDevice(c->device));
   if (pos0 + steps > c->next_pos || pos0 == 0) c->next_pos = pos0 + steps;      // (L2_CHECK_POS: rows 0 .. pos0 + steps - 1 are written when this returns)
-  c->h_tokpos[0] = first_token; c->h_tokpos[1] = pos0; c->h_tokpos[2] = 0; c->h_tokpos[3] = 0;
+  c->h_tokpos[0] = first_token; c->h_tokpos[1] = pos0; c->h_tokpos[2] = 0; c->h_tokpos[3] = (int)(++c->run_nonce & 0x7ffu);
+  note_awo_stream(c, pos0, steps);
   HIPCHK(hipMemcpyAsync(c->tokpos, c->h_tokpos, 4 * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemsetAsync(c->amax, 0, 8 * 16 * 8, c->stream));   // argmax keys: zero at the start of every run (an aborted sampled step may have left some)
   if (aql_usable(c)) {
@@ -1036,7 +1055,8 @@ extern "C" int l2_decode_sample(l2_ctx* c, int first_token, int pos0, int steps,
   // the classifier's argmax keys give the softmax its maximum; the serial A/B form takes its own and would leave them stale
   c->samp_amax = !c->tp_path && temperature > 0 && c->amax && !c->samp.serial;
   HIPCHK(hipMemsetAsync(c->amax, 0, 8 * 16 * 8, c->stream));   // "zero between tokens" holds whatever an earlier (aborted) run left
-  c->h_tokpos[0] = first_token; c->h_tokpos[1] = pos0; c->h_tokpos[2] = 0; c->h_tokpos[3] = 0;
+  c->h_tokpos[0] = first_token; c->h_tokpos[1] = pos0; c->h_tokpos[2] = 0; c->h_tokpos[3] = (int)(++c->run_nonce & 0x7ffu);
+  note_awo_stream(c, pos0, steps);
   HIPCHK(hipMemcpyAsync(c->tokpos, c->h_tokpos, 4 * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(c->samp.params, params, sizeof(params), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(c->samp.rng, rng_state, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
@@ -1156,7 +1176,7 @@ extern "C" int l2_set_option(l2_ctx* c, int key, int value) {
     case L2_OPT_PREFILL_F32_MFMA: c->opt_pf_f32 = !!value; return L2_OK;
     case L2_OPT_CHECK_POS: c->opt_pos_check = !!value; return L2_OK;
     case L2_OPT_PACKED_MIB: case L2_OPT_WEIGHT_MIB: case L2_OPT_SAMPLED_TOKENS: case L2_OPT_SAMPLED_SERIAL: case L2_OPT_SEQS:
-    case L2_OPT_BATCH_SAMPLED_TOKENS: case L2_OPT_BATCH_SAMPLED_SERIAL:
+    case L2_OPT_BATCH_SAMPLED_TOKENS: case L2_OPT_BATCH_SAMPLED_SERIAL: case L2_OPT_ATTN_WO_STREAM:
       return fail(L2_E_ARG, "option %d is read-only", key);
     default: return fail(L2_E_ARG, "unknown option %d", key);
   }
@@ -1172,6 +1192,7 @@ extern "C" int l2_get_option(l2_ctx* c, int key, int* value) {
     case L2_OPT_PREFILL_F32_MFMA: *value = c->opt_pf_f32; return L2_OK;
     case L2_OPT_CHECK_POS: *value = c->opt_pos_check; return L2_OK;
     case L2_OPT_SEQS: *value = c->bt ? c->bt->n_seqs : 0; return L2_OK;
+    case L2_OPT_ATTN_WO_STREAM: *value = c->last_awo_stream ? 1 : 0; return L2_OK;
     case L2_OPT_BATCH_SAMPLED_TOKENS: case L2_OPT_BATCH_SAMPLED_SERIAL: {
       const unsigned long long v = c->bt ? c->bt->smp_stats[key == L2_OPT_BATCH_SAMPLED_SERIAL ? 1 : 0] : 0;
       *value = v > 0x7fffffffull ? 0x7fffffff : (int)v;

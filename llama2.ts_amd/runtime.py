@@ -28,6 +28,7 @@ STATE_IDS = dict(x=S_X, xb=S_XB, xb2=S_XB2, hb=S_HB, hb2=S_HB2, q=S_Q, k=S_K, v=
 OPT_EXACT_ATTENTION, OPT_USE_GRAPH, OPT_KEEP_STATE, OPT_PACKED_MIB, OPT_WEIGHT_MIB, OPT_SAMPLED_TOKENS, OPT_SAMPLED_SERIAL, OPT_AQL_QUEUE, OPT_PREFILL_F32_MFMA, OPT_CHECK_POS = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 OPT_SEQS = 11      # read-only: sequences reserved by seq_reserve (0 before it)
 OPT_BATCH_SAMPLED_TOKENS, OPT_BATCH_SAMPLED_SERIAL = 12, 13   # read-only: decode_sample_batch's and step_batch's sampled tokens, of those by the serial loop
+OPT_ATTN_WO_STREAM = 14   # read-only: 1 when a step of the last forward / decode call ran attention and wo as one launch
 F_GQA, F_GENERATE_ROPE = 1, 2     # l2_create_ex flags
 TP_SOLO_ID = b"L2-SOLO-SHARD-TIMING"   # l2_create_tp id of a shard-timing context (include/llama2_hip.h: L2_TP_SOLO_ID)
 
