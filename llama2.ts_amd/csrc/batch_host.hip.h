@@ -172,17 +172,19 @@ static void bt_cls_weights(const l2_ctx* c, PfArgs& a) {
 }
 
 static hipError_t launch_bt_attn(const l2_ctx* c, const AttnArgs& a, const AttnRows& r, int n, hipStream_t st) {
-  const int lr = attn_lr(c->hs), nw = attn_nw(c);
-  const size_t lds = attn_tile_lds(c->S, 1, nw, nw == 8 ? 8 : 16);
-  const dim3 grid(c->H, n), block(64 * nw);
-#define L2_BT(LR, NW, NT) do { hipError_t e_ = lds_opt_in(&bt_attn_tile_kernel<LR, NW, NT>, lds); if (e_ != hipSuccess) return e_; \
+  const AttnTilePick t = attn_tile_pick(c->hs);
+  const size_t lds = attn_tile_lds(c->S, 1, t.nw, t.nt);
+  const dim3 grid(c->H, n), block(64 * t.nw);
+#define L2_BT(LR, NW, NT) do { if (t.nw != NW || t.nt != NT) return hipErrorInvalidValue; \
+                               hipError_t e_ = lds_opt_in(&bt_attn_tile_kernel<LR, NW, NT>, lds); if (e_ != hipSuccess) return e_; \
                                hipLaunchKernelGGL((bt_attn_tile_kernel<LR, NW, NT>), grid, block, lds, st, a, r); } while (0)
-  switch (lr) {      // the instances launch_attn_tile uses
+  switch (t.lr) {      // the instances launch_attn_tile uses
     case 4: L2_BT(4, 4, 16); break;
     case 8: L2_BT(8, 4, 16); break;
     case 16: L2_BT(16, 4, 16); break;
     case 32: L2_BT(32, 8, 8); break;
-    default: L2_BT(64, 4, 16); break;
+    case 64: L2_BT(64, 4, 16); break;
+    default: return hipErrorInvalidValue;
   }
 #undef L2_BT
   return hipGetLastError();
@@ -209,7 +211,7 @@ static int bt_classify(const l2_ctx* c, const float* x, float* xn, float* out, i
     memset(&a, 0, sizeof(a));
     bt_cls_weights(c, a);
     a.xin = xn + (size_t)s0 * c->d; a.out = out + (size_t)s0 * c->V; a.n = c->d; a.rows = c->V; a.dim = c->d; a.nvalid = ms;
-    bt_gemm<MODE_CLS_ROWS>(c, a, pf_tiles(ms).tt, st);
+    LCHK(launch_gemm<MODE_CLS_ROWS>(a, plan_gemm(plan_shape(c), plan_opts(c), PF_GEMM_BATCH, MODE_CLS_ROWS, a.rows, pf_tiles(ms)), st));
   }
   LCHK(hipGetLastError());
   return L2_OK;
@@ -406,7 +408,7 @@ extern "C" int l2_seq_prefill(l2_ctx* c, int seq, const int32_t* tokens, int n_t
   int rc = ensure_ready(c);
   if (rc) return rc;
   HIPCHK(hipSetDevice(c->device));
-  const int step = pf3_ok(c) ? PF_S * PF_T : PF_T;
+  const int step = plan_step(plan_shape(c), plan_opts(c));
   int done = 0;
   while (done < n_tokens) {
     const int n = (n_tokens - done < step) ? n_tokens - done : step;
@@ -563,7 +565,7 @@ static int bp_enqueue(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_to
   const PfActs& P = b->pact;
   int rc = pf_acts_ensure(c, b->pact);
   if (rc) return rc;
-  bp_plan(p, pf3_ok(c) ? (int)BP_ROWS : (int)PF_T, n, seqs, n_tokens, tokens, pos0, R, nd);
+  bp_plan(p, plan_step(plan_shape(c), plan_opts(c)), n, seqs, n_tokens, tokens, pos0, R, nd);
   rc = bp_upload(c, p);
   if (rc) return rc;
   const int* dseq = b->ptab;
@@ -574,19 +576,22 @@ static int bp_enqueue(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_to
   for (int k = 0; k < p.nl; ++k) {
     const int r0 = k * p.step, m = (int)std::min<size_t>(p.step, R - r0), nti = p.tile0[k + 1] - p.tile0[k];
     const int ndk = k == 0 ? nd : 0;                           // decode rows of this launch sequence (its rows 0 .. ndk-1)
-    const size_t alds = pf_attn_lds(p.maxp[k] + 15);      // the longest tile's keys
-    const bool mfma = attn_mfma_ok(c, alds);
+    AttnPick ap[2];      // the longest tile's keys size the MFMA form's LDS
+    const int nap = plan_attention(plan_shape(c), plan_opts(c), CALL_PACKED, m, ndk, p.maxp[k] + 15, ap);
     const AttnRows rows = {dseq + r0, dpos + r0, b->d_kc, b->d_vc, 0};
     // attention: 16-query tiles on the fp64 MFMA (decode rows: per (head, row)), or the decode form per (head, row) for every row where
     // prefill_chunk takes it
     const auto attn = [&](int l, size_t loff) -> int {
-      const int nrow = mfma ? ndk : m;
-      if (nrow > 0) { const int e = bt_attn_rows(c, l, P, rows, loff, nrow, st); if (e) return e; }
-      if (!mfma || nti == 0) return L2_OK;
-      BpAttnArgs pa;
-      pa.q = P.q; pa.xb = P.xb; pa.seq_kc = b->d_kc; pa.seq_vc = b->d_vc; pa.seq_loff = loff; pa.tiles = dtiles + p.tile0[k];
-      pa.dim = c->d; pa.seq_len = c->S; pa.inv_sqrt_hs = 1.0 / sqrt((double)c->hs);
-      return launch_attn_mfma(c, bp_attn_mfma_kernel<64>, bp_attn_mfma_kernel<128>, dim3(c->H, nti), alds, pa, st);
+      for (int i = 0; i < nap; ++i) {
+        if (ap[i].family == AT_BT_TILE) { const int e = bt_attn_rows(c, l, P, rows, loff, ap[i].rows, st); if (e) return e; continue; }
+        if (nti == 0) return fail(L2_E_HIP, "packed attention: %d tile rows planned, no tile cut", ap[i].rows);
+        BpAttnArgs pa;
+        pa.q = P.q; pa.xb = P.xb; pa.seq_kc = b->d_kc; pa.seq_vc = b->d_vc; pa.seq_loff = loff; pa.tiles = dtiles + p.tile0[k];
+        pa.dim = c->d; pa.seq_len = c->S; pa.inv_sqrt_hs = 1.0 / sqrt((double)c->hs);
+        const int e = launch_attn_mfma(ap[i], bp_attn_mfma_kernel<64>, bp_attn_mfma_kernel<128>, dim3(c->H, nti), pa, st);
+        if (e) return e;
+      }
+      return L2_OK;
     };
     rc = pf_layers<PF_GEMM_PROMPT>(c, P, dtok + r0, m, rows, attn, st);
     if (rc) return rc;

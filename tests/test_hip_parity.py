@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import batch_shapes
 import oracle_lib as O
 import sum_cases
 from llama2_ts_amd import configs, runtime
@@ -136,12 +137,20 @@ def _random_headers(count, seed):
 WIDE_SHAPES = [(512, 640, 1, 2, 2, 300, 150), (384, 1000, 2, 2, 2, -211, 40), (1792, 2304, 1, 14, 14, 257, 24), (2048, 1600, 1, 16, 16, -130, 20)]
 
 
-@pytest.mark.parametrize("hdr", _random_headers(14, 20261003) + WIDE_SHAPES)
+# ... and three head sizes of the batch shape sweep (tests/batch_shapes.py: 20, 36, 192) through the decode path
+SWEEP_SHAPES = [batch_shapes.SHAPES[n] for n in ("hs20", "hs36", "hs192")]
+# (dim, hidden) of the random / wide shapes above whose prompt runs the prompt kernels; on the others l2_prefill is l2_forward per token
+PROMPT_KERNEL_SHAPES = {(64, 112), (512, 640), (1792, 2304), (2048, 1600)}
+
+
+@pytest.mark.parametrize("hdr", _random_headers(14, 20261003) + WIDE_SHAPES + SWEEP_SHAPES)
 def test_random_shapes_match_the_oracle(built, hdr):
     """Shapes nobody tuned for -- odd hidden sizes, head sizes that are not powers of two or not multiples of 4 (scalar kernels),
     one head, vocabularies that are not multiples of anything, shared and unshared classifiers, contexts shorter than a tile --
     against the oracle (itself pinned to the reference): logits <= 1e-4 and the same argmax at every step of the whole context
-    (up to 40 steps), l2_forward and the device greedy loop, then the same prompt through l2_prefill."""
+    (up to 40 steps), l2_forward and the device greedy loop, then the same prompt through l2_prefill.  Whether that last leg runs the
+    prompt kernels is the launch plan's answer (l2_debug_batch_plan): where it does, the prompt's cache rows are held to the oracle's too;
+    where it does not, l2_prefill is the decode step per token and the leg only checks that it says so."""
     orc = O.Oracle(hdr, 7)
     ctx = runtime.Context(hdr)
     upload_from_oracle(ctx, orc)
@@ -159,7 +168,20 @@ def test_random_shapes_match_the_oracle(built, hdr):
     upload_from_oracle(b, orc)
     lp = b.prefill(fed, 0)
     assert np.abs(lp - want).max() <= TOL and runtime.argmax(lp) == tok
+    prompt_kernels = batch_shapes.reaches_prompt_kernels(hdr)
+    assert prompt_kernels or (hdr[0], hdr[1]) not in PROMPT_KERNEL_SHAPES and hdr not in SWEEP_SHAPES, (hdr, "was meant to reach the prompt kernels")
+    if prompt_kernels:
+        d, L, S = hdr[0], hdr[2], hdr[6]
+        for name in ("key_cache", "value_cache"):
+            got_c = b.read_state(name).reshape(L, S, d)[:, :steps]
+            assert np.abs(got_c - orc.state(name).reshape(L, S, d)[:, :steps]).max() <= TOL, (hdr, name)
     ctx.close(); b.close(); orc.close()
+
+
+def test_the_prefill_leg_of_the_random_shapes_reaches_the_prompt_kernels(built):
+    """At least the four random / wide shapes counted by hand and the three sweep shapes take the prompt kernels in the leg above."""
+    reach = {(h[0], h[1]) for h in _random_headers(14, 20261003) + WIDE_SHAPES + SWEEP_SHAPES if batch_shapes.reaches_prompt_kernels(h)}
+    assert PROMPT_KERNEL_SHAPES | {(h[0], h[1]) for h in SWEEP_SHAPES} <= reach, reach
 
 
 def test_full_llama2_7b_matches_reference_golden(built):
