@@ -7,7 +7,7 @@
 // lives in device tables -- row t feeds token tok[t] at position pos[t] of sequence seq[t] -- read by the q / k / v epilogue (RoPE
 // and the cache stores: pf_emit<MODE_QKV_ROWS>), the attention kernel (attention.hip.h: bt_attn_tile_kernel, one workgroup per
 // (head, row) over that row's own cache) and the per-row pick below, so one recorded step serves every placement of the sequences.
-// The sampled step (l2_decode_sample_batch) ends with the row form of the device sampler (sampler.h: BatchSampler) and bt_pick_kernel.
+// The sampled step (l2_decode_sample_batch) ends with the row form of the device sampler (sampler.h: RowSampler) and bt_pick_kernel.
 // The step runs as a replayed hipGraph or eager launches on the context's stream, never on the library's AQL queue: every kernel
 // boundary carries the usual acquire / release, and the tables the pick advances are read with plain loads by the next step.
 // Packed prompts (l2_seq_prefill_batch) run prefill's launch sequence over several sequences' prompt rows at once: the same per-row
@@ -24,7 +24,7 @@ __global__ void __launch_bounds__(1024) bt_argmax_kernel(const float* logits, in
 }
 
 // The sampled step's last launch: row r takes its argmax when its temperature params[2 r] is 0 (no draw), else the token the row
-// sampler left in pick[4 r] (sampler.h: BatchSampler); every row's pick is applied exactly once, as bt_argmax_kernel does it.
+// sampler left in pick[4 r] (sampler.h: RowSampler); every row's pick is applied exactly once, as bt_argmax_kernel does it.
 __global__ void __launch_bounds__(1024) bt_pick_kernel(const float* logits, int V, const double* params, int* pick, int* tok, int* pos, const int* start,
                                                        int* out, int out_stride) {
   if (params[2 * blockIdx.x] != 0.0) {

@@ -25,7 +25,7 @@ struct BatchState {
   float* logits = nullptr;                // [BT_MAX][V]
   hipGraphExec_t g[BT_MAX + 1] = {};      // the recorded step per row count
   hipGraphExec_t gs[BT_MAX + 1] = {};     // the recorded sampled step per row count (forward + row sampler + bt_pick_kernel)
-  l2s::BatchSampler* smp = nullptr;       // the row sampler's buffers: allocated at the first l2_decode_sample_batch
+  l2s::RowSampler* smp = nullptr;         // the row sampler's buffers: allocated at the first l2_decode_sample_batch
   unsigned long long smp_stats[2] = {};   // {tokens sampled, of those by the serial loop} over every l2_decode_sample_batch
   std::vector<uintptr_t> sig;             // what the recorded steps baked in (weight addresses, options)
   // Packed prompts (l2_seq_prefill_batch), allocated at its first call: activations of one launch sequence, and the call's tables
@@ -232,7 +232,7 @@ static int bt_forward(l2_ctx* c, int n, hipStream_t st) {
 static int bt_enqueue_pick(l2_ctx* c, int n, bool sampled, hipStream_t st) {
   BatchState* b = c->bt;
   if (sampled) {
-    LCHK(l2s::enqueue_rows(*b->smp, b->logits, n, st));
+    LCHK(l2s::enqueue_rows(*b->smp, b->logits, n, l2s::PICK_BOTH, l2s::Pick{b->smp->pick, nullptr, nullptr}, st));
     hipLaunchKernelGGL(bt_pick_kernel, dim3(n), dim3(1024), 0, st, (const float*)b->logits, c->V, (const double*)b->smp->params, b->smp->pick,
                        b->tok_of(), b->pos_of(), (const int*)b->start_of(), b->out, c->S);
   } else {
@@ -263,7 +263,7 @@ struct BtSampling { const double *temperature, *topp; uint64_t* rng_state; };
 
 // Stage the settings and rng states of n rows (row j: the call's row ord[j]; null: j) in the row sampler's pinned tables -- the stream has
 // been synchronised since the previous call's copies -- and upload them.
-static int bt_sampler_upload(const l2s::BatchSampler& sm, int n, const BtSampling& s, const int* ord, hipStream_t st) {
+static int bt_sampler_upload(const l2s::RowSampler& sm, int n, const BtSampling& s, const int* ord, hipStream_t st) {
   for (int j = 0; j < n; ++j) {
     const int i = ord ? ord[j] : j;
     sm.h_params[2 * j] = s.temperature[i]; sm.h_params[2 * j + 1] = s.topp[i]; sm.h_rng[j] = s.rng_state[i];
@@ -275,7 +275,7 @@ static int bt_sampler_upload(const l2s::BatchSampler& sm, int n, const BtSamplin
 }
 
 // The way back: enqueue the copies of the rows' rng states and counters into the pinned tables ...
-static int bt_sampler_fetch(const l2s::BatchSampler& sm, int n, hipStream_t st) {
+static int bt_sampler_fetch(const l2s::RowSampler& sm, int n, hipStream_t st) {
   HIPCHK(hipMemcpyAsync(sm.h_rng, sm.rng, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(sm.h_stats, sm.stats, 2 * (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   return L2_OK;
@@ -362,7 +362,7 @@ extern "C" int l2_decode_greedy_batch(l2_ctx* c, int n, const int32_t* seqs, con
 static int bt_ensure_sampler(l2_ctx* c, const char* who) {
   BatchState* b = c->bt;
   if (b->smp) return L2_OK;
-  l2s::BatchSampler* sm = new l2s::BatchSampler();
+  l2s::RowSampler* sm = new l2s::RowSampler();
   const hipError_t e = l2s::create_rows(sm, c->V, b->n_seqs);
   if (e != hipSuccess) { delete sm; (void)hipGetLastError(); return fail(L2_E_HIP, "%s: device memory for the row sampler: %s", who, hipGetErrorString(e)); }
   b->smp = sm;

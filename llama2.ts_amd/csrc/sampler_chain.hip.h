@@ -161,8 +161,14 @@ __device__ __forceinline__ void tile_scan(const float (&v)[IT], double base, Til
 __device__ __forceinline__ unsigned order_key(float x) { const unsigned b = __float_as_uint(x); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 __device__ __forceinline__ float order_value(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
+// The margin form's phases are launched once for rows 0 .. n-1 (sampler.h: RowSampler), the row on blockIdx.y (the rank merge: blockIdx.z)
+// and every per-row buffer at a row stride; a single sequence is one row.  A row whose mode (row_mode) a phase does not serve leaves at entry.
+
 // max over state.logits[q] / temperature (:482, softmax :183-186)
-__device__ __forceinline__ void scaled_max_body(const float* logits, int V, const double* params, unsigned* mxkey) {
+__global__ void __launch_bounds__(TN) scaled_max_rows_kernel(const float* logits, int V, const double* params, unsigned* mxkey) {
+  const int r = blockIdx.y;
+  if (row_mode(params + 2 * r) == 0) return;
+  logits += (size_t)r * V; params += 2 * r; mxkey += r;
   float v[IT];
   load_tile(logits, V, blockIdx.x, v);
   const double T = params[0];
@@ -174,15 +180,16 @@ __device__ __forceinline__ void scaled_max_body(const float* logits, int V, cons
   for (int off = 32; off > 0; off >>= 1) key = max(key, (unsigned)__shfl_xor((int)key, off, 64));
   if ((threadIdx.x & 63) == 0) atomicMax(mxkey, key);
 }
-__global__ void __launch_bounds__(TN) scaled_max_kernel(const float* logits, int V, const double* params, unsigned* mxkey) {
-  scaled_max_body(logits, V, params, mxkey);
-}
 
 // probs[i] = (float)exp(x_i - max)  (:187) and the tile sums for the approximate prefix
-// (amax != null, temperature > 0: the classifier already folded max(logits) into its argmax keys -- kernels.hip.h
+// (amax != null, one row, temperature > 0: the classifier already folded max(logits) into its argmax keys -- kernels.hip.h
 // argmax_key -- and x -> (float)(x / T) is monotone, so the maximum of the scaled logits is the scaled maximum)
-__device__ __forceinline__ void exp_body(const float* logits, int V, const double* params, const unsigned* mxkey, const unsigned long long* amax,
-                                         float* probs, double* part, double* wsum) {
+__global__ void __launch_bounds__(TN) exp_rows_kernel(const float* logits, int V, const double* params, const unsigned* mxkey, const unsigned long long* amax,
+                                                       float* probs, double* part, size_t P, int G) {
+  __shared__ double wsum[NWV];
+  const int r = blockIdx.y;
+  if (row_mode(params + 2 * r) == 0) return;
+  logits += (size_t)r * V; params += 2 * r; mxkey += r; probs += r * P; part += (size_t)r * G;
   float v[IT];
   load_tile(logits, V, blockIdx.x, v);
   const double T = params[0];
@@ -204,11 +211,6 @@ __device__ __forceinline__ void exp_body(const float* logits, int V, const doubl
   }
   const double t = tile_total(v, wsum);
   if (threadIdx.x == 0) part[blockIdx.x] = t;
-}
-__global__ void __launch_bounds__(TN) exp_kernel(const float* logits, int V, const double* params, const unsigned* mxkey, const unsigned long long* amax,
-                                                  float* probs, double* part) {
-  __shared__ double wsum[NWV];
-  exp_body(logits, V, params, mxkey, amax, probs, part, wsum);
 }
 
 __global__ void __launch_bounds__(TN) tile_sums_kernel(const float* x, int V, double* part) {
@@ -537,9 +539,32 @@ __global__ void __launch_bounds__(TN) chain_kernel(ChainArgs a) {
 
 // Runs of the exps and, by the last workgroup to finish, their exact total (the softmax denominator, :189): the records go out as
 // write-through stores, every wave drains them, one lane takes a ticket; the workgroup that gets the last one walks the chain.
-__global__ void __launch_bounds__(TN) runs_total_kernel(ChainArgs a, Run* recs, int* cnt, unsigned* ticket, double* total) {
+__global__ void __launch_bounds__(TN) runs_total_rows_kernel(ChainArgs rows, size_t P, size_t R, const double* params, Run* recs0, int* cnt0, unsigned* ticket0,
+                                                              double* total0) {
+  const int r = blockIdx.y;
+  if (row_mode(params + 2 * r) != 2) return;
+  const size_t g = (size_t)r * rows.G;
+  ChainArgs a = rows;
+  a.x += r * P; a.part += g; a.recs += r * R; a.cnt += g; a.S += r * R; a.End += r * R; a.Bad += r * R;
+  Run* const recs = recs0 + r * R;
+  int* const cnt = cnt0 + g;
+  unsigned* const ticket = ticket0 + r;
+  double* const total = total0 + r;
   __shared__ ChainShared sh;
-#include "runs_total_body.inc"
+  float v[IT];
+  load_tile(a.x, a.V, blockIdx.x, v);
+  Elems el;
+  tile_scan(v, tile_base(a.part, blockIdx.x), sh.tile, el);
+  emit_runs<false, true>(el, v, a.V, blockIdx.x, recs, cnt, nullptr, nullptr);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) sh.slot = (int)__hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  if (sh.slot != a.G - 1) return;
+  __syncthreads();
+  bool in_lds;
+  chain_total<true>(a, sh, &in_lds);
+  if (threadIdx.x == 0) { *total = sh.val; __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 }
 
 // The exact softmax denominator, recomputed by every workgroup of the kernel that needs it next (a walk over ~50 runs is

@@ -23,7 +23,7 @@
 // needs the exact probabilities, so its first half stays the exact chain of sampler_chain.hip.h.
 
 struct MarginArgs {
-  const float* exps;             // (V) fp32 exps of the scaled logits (exp_kernel)
+  const float* exps;             // (V) fp32 exps of the scaled logits (exp_rows_kernel)
   const double* part;            // (G) their tile sums
   int V, G;
   double* part2;                 // (G) tile sums of the probabilities (plain sample), written and read inside one launch
@@ -34,10 +34,10 @@ struct MarginArgs {
   double* part_sorted;           //   zero between tokens
   const double* params;          // {temperature, topp}
   unsigned long long* rng;
-  int* tokpos;
+  int* tokpos;                   // the caller's {token, pos, step} with tokens_out, or the rows' pick records (margin_row)
   int* tokens_out;
   unsigned* mxkey;               // reset for the next token
-  unsigned long long* amax;      // or the classifier's 8 argmax keys
+  unsigned long long* amax;      // or the classifier's 8 argmax keys (one row)
   unsigned long long* stats;     // {tokens, tokens that took the serial loop}
   int force_serial;
 };
@@ -196,14 +196,108 @@ __device__ __forceinline__ void pick_done(const MarginArgs& a, int token, bool s
   if (a.amax && tid < 8) a.amax[(size_t)tid * 16] = 0ull;
 }
 
-// ---- plain sample(): probabilities' tile sums by every workgroup, the pick by the last one to arrive ----------------------------
-__global__ void __launch_bounds__(TN) sample_margin_kernel(const MarginArgs a) {
-  __shared__ MarginShared sh;
-#include "sample_margin_body.inc"
+// Row r's view of the margin arguments (a: row 0's pointers).  The pick goes through advance(): into the caller's tokens_out[step] with
+// {token, pos, step} advanced in tokpos (one row, l2_decode_sample), or -- no tokens_out -- into the row's record pick[4 r ..]
+// {token, count, step, token} whose step bt_pick_kernel puts back to 0.  amax (the classifier's argmax keys) is the one-row caller's.
+__device__ __forceinline__ MarginArgs margin_row(const MarginArgs& a, int r, size_t P) {
+  MarginArgs m = a;
+  const size_t g = (size_t)r * a.G;
+  m.exps = a.exps + r * P; m.part = a.part + g; m.part2 = a.part2 + g; m.amb = a.amb + g; m.ticket = a.ticket + r;
+  m.sorted = a.sorted + r * P; m.ids = a.ids + r * P; m.part_sorted = a.part_sorted + g; m.params = a.params + 2 * r; m.rng = a.rng + r;
+  m.tokpos = a.tokpos + 4 * r; m.tokens_out = a.tokens_out ? a.tokens_out : a.tokpos + 4 * r + 3; m.mxkey = a.mxkey + r; m.stats = a.stats + 2 * r;
+  return m;
 }
 
-// ---- sample_topp() behind the sort: one workgroup ------------------------------------------------------------------------------
-__global__ void __launch_bounds__(TN) topp_margin_kernel(const MarginArgs a) {
+// ---- plain sample(): probabilities' tile sums by every workgroup, the pick by the last one to arrive ----------------------------
+__global__ void __launch_bounds__(TN) sample_margin_rows_kernel(const MarginArgs rows, size_t P) {
+  if (row_mode(rows.params + 2 * blockIdx.y) != 1) return;
+  const MarginArgs a = margin_row(rows, blockIdx.y, P);
   __shared__ MarginShared sh;
-#include "topp_margin_body.inc"
+  const int tid = threadIdx.x, tile = blockIdx.x, n = a.V;
+  const double T = tile_base(a.part, a.G);                     // tree total of the exps: the same bits in every lane of every workgroup
+  const int win = mr::window(n);
+  float v[IT];
+  load_tile(a.exps, n, tile, v);
+  double amb = 0.0;
+#pragma unroll
+  for (int k = 0; k < IT; ++k) v[k] = mr::quotient_checked(v[k], T, win, &amb);      // padding: e = 0 -> p = 0
+  const double t = tile_total(v, sh.wsum);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) amb += __shfl_xor(amb, off, 64);
+  if ((tid & 63) == 0) sh.wamb[tid >> 6] = amb;
+  __syncthreads();
+  if (tid == 0) {
+    // write-through stores another CU's L1-bypassing loads see, drained before the ticket is taken (MI355X_MICROARCH.md, hand-off forms)
+    __hip_atomic_store(a.part2 + tile, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(a.amb + tile, (sh.wamb[0] + sh.wamb[1]) + (sh.wamb[2] + sh.wamb[3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    sh.slot[3] = (int)__hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  if (sh.slot[3] != a.G - 1) return;
+  // ---- the last workgroup: every tile's sums are in memory
+  const double own = tid < a.G ? __hip_atomic_load(a.part2 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+  const double own_amb = tid < a.G ? __hip_atomic_load(a.amb + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+  double Qn, A;
+  const double incl = block_scan(own, sh.wsum, &Qn);
+  block_scan(own_amb, sh.wamb, &A);
+  if (tid == 0) { sh.val[1] = (double)random_f32(a.rng); __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }   // past the L2, where the adds are made
+  __syncthreads();
+  const double u = sh.val[1];
+  const double M = mr::margin(n, Qn, A);
+  auto prob = [&](int i) { return (float)((double)a.exps[i] / T); };
+  int hit = -2;
+  double qhit;
+  if (!a.force_serial && Qn > 0.0 && Qn <= 1.7976931348623157e308) hit = decide_first(prob, n, a.G, u * Qn, M, n, incl, own, sh, &qhit);   // randValue = random_f32() * sum (:370)
+  const bool serial = hit == -2;
+  if (serial) {                                                // llama2.ts:189-192, :368-376 as written
+    double total, sum;
+    serial_sum([&](int i) { return a.exps[i]; }, n, sh, &total, false, INFINITY);
+    auto p = [&](int i) { return (float)((double)a.exps[i] / total); };
+    serial_sum(p, n, sh, &sum, true, INFINITY);
+    hit = serial_first(p, n, u * sum, sh);
+  }
+  pick_done(a, hit < 0 ? 0 : hit, serial);                     // fall-through returns 0 (:375)
+}
+
+// ---- sample_topp() behind the sort: one workgroup per row ----------------------------------------------------------------------
+__global__ void __launch_bounds__(TN) topp_margin_rows_kernel(const MarginArgs rows, size_t P) {
+  if (row_mode(rows.params + 2 * blockIdx.y) != 2) return;
+  const MarginArgs a = margin_row(rows, blockIdx.y, P);
+  __shared__ MarginShared sh;
+  const int tid = threadIdx.x, n = a.V;
+  const double topp = a.params[1];
+  const double own = tid < a.G ? a.part_sorted[tid] : 0.0;
+  double Qn;
+  const double incl = block_scan(own, sh.wsum, &Qn);
+  if (tid == 0) sh.val[1] = (double)random_f32(a.rng);
+  __syncthreads();
+  if (tid < a.G) a.part_sorted[tid] = 0.0;
+  const double u = sh.val[1];
+  const double M = mr::margin(n, Qn, 0.0);
+  auto sorted = [&](int i) { return a.sorted[i]; };
+  int token = 0;
+  bool serial = a.force_serial || !(Qn > 0.0 && Qn <= 1.7976931348623157e308);
+  if (!serial) {
+    // cumProb > topp (:385): `topp < cum_i` with an exact constant
+    double qc;
+    const int c = decide_first(sorted, n, a.G, topp, M, n, incl, own, sh, &qc);
+    if (c == -2) serial = true;
+    else if (c <= 0) token = 0;                                // never crossed (lastIdx stays 0, :383) or crossed by the first: the second loop is empty
+    else {
+      __syncthreads();
+      double qh;
+      const int hit = decide_first(sorted, n, a.G, u * qc, 2.0 * M, c, incl, own, sh, &qh);   // cumProb as the loop left it (:388), i < lastIdx only (:390)
+      if (hit == -2) serial = true;
+      else token = hit < 0 ? 0 : a.ids[hit];
+    }
+  }
+  if (serial) {                                                // llama2.ts:382-393 as written
+    double cum;
+    const int at = serial_sum(sorted, n, sh, &cum, true, topp);
+    const int last = at < 0 ? 0 : at;
+    const int hit = serial_first(sorted, last, u * cum, sh);
+    token = hit < 0 ? 0 : a.ids[hit];
+  }
+  pick_done(a, token, serial);
 }

@@ -69,11 +69,16 @@ __global__ void __launch_bounds__(TN) sort_tile_kernel(ChainArgs a, const float*
   }
 }
 
-// The same tile sort by 1024 threads with one key each and the exact total handed in (runs_total_kernel): four waves per SIMD hide the
+// The same tile sort by 1024 threads with one key each and the exact total handed in (runs_total_rows_kernel): four waves per SIMD hide the
 // lane exchanges one wave per SIMD waits for, and no thread carries four 64-bit keys through 55 stages.
 constexpr int WT = 1024;
 static_assert(WT == STILE, "one key per thread");
-__device__ __forceinline__ void sort_tile_wide_body(const float* exps, const double* total, int V, float* run_p, int* run_id, u64* xch) {
+__global__ void __launch_bounds__(WT) sort_tile_wide_rows_kernel(const float* exps, const double* total, int V, float* run_p, int* run_id, size_t P,
+                                                                  const double* params) {
+  __shared__ u64 xch[STILE];
+  const int r = blockIdx.y;
+  if (row_mode(params + 2 * r) != 2) return;
+  exps += r * P; total += r; run_p += r * P; run_id += r * P;
   const int tid = threadIdx.x, i = blockIdx.x * STILE + tid;
   const double s = *total;
   const float p = (i < V) ? (float)((double)exps[i] / s) : 0.0f;                  // :192
@@ -99,10 +104,6 @@ __device__ __forceinline__ void sort_tile_wide_body(const float* exps, const dou
   run_p[i] = pad ? -1.0f : __uint_as_float(0xffffffffu - (unsigned)(v >> 32));
   run_id[i] = pad ? -1 : (int)(unsigned)v;
 }
-__global__ void __launch_bounds__(WT) sort_tile_wide_kernel(const float* exps, const double* total, int V, float* run_p, int* run_id) {
-  __shared__ u64 xch[STILE];
-  sort_tile_wide_body(exps, total, V, run_p, run_id, xch);
-}
 
 // Every element's place in the merged order: its place in its own tile + the number of elements of every other tile in front of it
 // (ties: the tile with the smaller ids first), by binary search in sorted tiles held in LDS.  The searches are what the kernel costs
@@ -113,8 +114,61 @@ constexpr int RT = 512;                                           // threads = e
 constexpr int RANK_TQ = 8;                                        // sorted tiles a workgroup searches (32 KB of LDS)
 // Also adds every element to the sum of the tile of the merged order it lands in (part[], zero on entry): the approximate
 // prefix of the next stage.  fp64 atomics in no fixed order -- the prefix only has to be approximate.
-__global__ void __launch_bounds__(RT) sort_rank_kernel(const float* run_p, const int* run_id, int GS, int G, unsigned* acc, float* sorted, int* ids, double* part) {
+__global__ void __launch_bounds__(RT) sort_rank_rows_kernel(const float* run_p0, const int* run_id0, int GS, int G, unsigned* acc0, float* sorted0, int* ids0,
+                                                             double* part0, size_t P, const double* params) {
+  const size_t r = blockIdx.z;
+  if (row_mode(params + 2 * r) != 2) return;
+  const float* const run_p = run_p0 + r * P;
+  const int* const run_id = run_id0 + r * P;
+  unsigned* const acc = acc0 + r * P;
+  float* const sorted = sorted0 + r * P;
+  int* const ids = ids0 + r * P;
+  double* const part = part0 + r * G;
   __shared__ int lds_p[RANK_TQ * STILE];                        // probability bit patterns of the group's tiles (pads: negative)
   __shared__ double lpart[MAX_VOCAB / TILE];
-#include "sort_rank_body.inc"
+  const int tid = threadIdx.x, n = GS * STILE;
+  for (int j = tid; j < G; j += RT) lpart[j] = 0.0;
+  const int e = blockIdx.x * RT + tid;
+  const int mine = e < n ? reinterpret_cast<const int*>(run_p)[e] : -1;
+  const int own = e / STILE;
+  const int g0 = blockIdx.y * RANK_TQ, gt = min(RANK_TQ, GS - g0), gn = gt * STILE, groups = gridDim.y;
+  {
+    // one 16-byte load in flight per thread (deeper queues measured slower), every workgroup starting at another tile
+    const int* src = reinterpret_cast<const int*>(run_p) + (size_t)g0 * STILE;
+    const int rot = (int)(blockIdx.x % (unsigned)gt) * STILE;
+    for (int j = tid * 4; j < gn; j += RT * 4) { int jj = j + rot; if (jj >= gn) jj -= gn; *reinterpret_cast<int4*>(lds_p + jj) = *reinterpret_cast<const int4*>(src + jj); }
+  }
+  __syncthreads();
+  if (mine >= 0) {                                              // not a pad
+    int lo[RANK_TQ], thr[RANK_TQ];
+#pragma unroll
+    for (int u = 0; u < RANK_TQ; ++u) {
+      const int b = min(u, gt - 1);
+      lo[u] = b * STILE;
+      thr[u] = mine - (g0 + b < own ? 1 : 0);                   // earlier tile: elements >= mine come first; later tile: only > mine
+    }
+#pragma unroll
+    for (int s = STILE / 2; s > 0; s >>= 1) {
+#pragma unroll
+      for (int u = 0; u < RANK_TQ; ++u) if (lds_p[lo[u] + s - 1] > thr[u]) lo[u] += s;
+    }
+    unsigned count = (own >= g0 && own < g0 + gt) ? (unsigned)(e - own * STILE) : 0u;   // its place in its own tile, counted once
+#pragma unroll
+    for (int u = 0; u < RANK_TQ; ++u) {
+      const int b = min(u, gt - 1);
+      int cnt = lo[u] - b * STILE;
+      if (cnt == STILE - 1 && lds_p[lo[u]] > thr[u]) cnt = STILE;
+      if (u < gt && g0 + b != own) count += (unsigned)cnt;
+    }
+    const unsigned before = groups > 1 ? atomicAdd(acc + e, count + (1u << 24)) : 0u;
+    if ((int)(before >> 24) == groups - 1) {                     // every other group has reported: the rank is complete
+      const int rank = (int)((before & 0xffffffu) + count);
+      if (groups > 1) __hip_atomic_store(acc + e, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // past the L2, like the adds
+      sorted[rank] = __int_as_float(mine);
+      ids[rank] = run_id[e];
+      atomicAdd(lpart + rank / TILE, (double)__int_as_float(mine));
+    }
+  }
+  __syncthreads();
+  for (int j = tid; j < G; j += RT) if (lpart[j] != 0.0) atomicAdd(part + j, lpart[j]);
 }

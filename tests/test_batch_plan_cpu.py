@@ -4,16 +4,14 @@ objects (symbol names only): every instance the plan selects exists; no instance
 that nothing selects; and the case table of the shape sweep (tests/batch_shapes.py, run on the GPU by tests/test_batch_shapes_gpu.py)
 selects every one of them and reaches every runtime branch the plan reports -- so an edit of that table cannot quietly drop coverage.
 A fourth test holds the sweep's token streams to few near-ties of the oracle's two largest logits (the argmax is not asserted there)."""
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import batch_shapes as B
-from llama2_ts_amd import configs, runtime
+import code_objects
+from llama2_ts_amd import configs
 
 FAMILIES = {
     "pf_gemm_kernel": r"14pf_gemm_kernelILi(\d+)ELi(\d+)ELi(\d+)EE",
@@ -31,20 +29,7 @@ INLINE_TEST_HEADERS = [(256, 512, 2, 4, 4, 1007, 64), (128, 384, 2, 2, 2, -600, 
 
 @pytest.fixture(scope="module")
 def built(tmp_path_factory):
-    import __graft_entry__ as graft
-    graft.build()
-    objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    if not (os.path.exists(objdump) and os.path.exists(readelf)):
-        pytest.skip("no ROCm llvm tools here")
-    tmp = tmp_path_factory.mktemp("co")
-    so = tmp / "lib.so"
-    shutil.copy(runtime.LIB_PATH, so)
-    subprocess.run([objdump, "--offloading", str(so)], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, cwd=str(tmp))
-    names = set()
-    for o in os.listdir(tmp):
-        if "gfx950" in o:
-            notes = subprocess.check_output([readelf, "--notes", str(tmp / o)]).decode()
-            names |= set(re.findall(r"\.name:\s+(_Z\S+)", notes))
+    names = code_objects.kernel_names(tmp_path_factory.mktemp("co"))
     inst = {(fam, tuple(int(v) for v in ((m,) if isinstance(m, str) else m))) for fam, rx in FAMILIES.items() for n in names for m in re.findall(rx, n)}
     assert len(inst) > 40 and all(any(i[0] == fam for i in inst) for fam in FAMILIES), sorted(inst)
     return inst
