@@ -29,7 +29,8 @@ extern "C" {
  * version step: it only adds, and a binding detects it by the presence of the l2_seq_reserve symbol.  So did its sampled loop
  * (l2_decode_sample_batch, option keys L2_OPT_BATCH_SAMPLED_TOKENS / _SERIAL), detected by its own symbol, and so were the packed
  * prompts (l2_seq_prefill_batch) and the mixed step (l2_step_batch), the per-token log-probabilities (l2_seq_score_batch,
- * l2_step_batch_logprobs), and so is the cache prefix copy (its one call is declared below, beside the cache read). */
+ * l2_step_batch_logprobs), constrained picks (l2_step_batch_constrained), and so is the cache prefix copy (its one call is declared
+ * below, beside the cache read). */
 #define L2_ABI_VERSION 5
 
 enum {
@@ -288,6 +289,37 @@ int l2_seq_score_batch(l2_ctx* ctx, int n, const int32_t* seqs, const int32_t* n
 int l2_step_batch_logprobs(l2_ctx* ctx, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
                            const double* temperature, const double* topp, uint64_t* rng_state, int32_t* picks_out, float* logits_out,
                            int top_k, double* pick_lp_out, int32_t* top_ids_out, double* top_lp_out);
+/* Constrained decoding: l2_step_batch_logprobs (pick_lp_out given) or l2_step_batch (pick_lp_out NULL: no log-probabilities, top_k
+ * must be 0 and the top arrays are ignored) with a token mask and / or a logit bias list per row.  For such a row the logits of its
+ * run's last position are rewritten on the device, after the classifier and before anything reads them:
+ *   x'[j] = -inf                    the row has a mask and bit j of it is clear
+ *   x'[j] = (float)(x[j] + bias_j)  j is allowed and in the row's bias list (one fp32 add)
+ *   x'[j] = x[j]                    otherwise, bit for bit
+ * and everything downstream sees x' and nothing else: the argmax, temperature scaling, softmax, `sample` / `sample_topp`, logits_out,
+ * pick_lp_out and the top-k lists -- the log-probabilities are those of the constrained, renormalised distribution; disallowed ids
+ * have lp -inf and sort last by ascending id (l2_seq_score_batch's rule for -inf logits).  The pick is what the reference's loop
+ * (llama2.ts:476-493) returns when state.logits holds x', one draw per sampled row, with ONE rule on top: if the returned id is one
+ * the row's mask does not allow -- only the `return 0` of llama2.ts:375 / :393 can be, e.g. whenever the most likely token alone
+ * crosses topp -- the row's pick is the first maximum of x' (llama2.ts:364-366).  The draw has still been made and rng_state[i] is
+ * what the reference would leave.  When id 0 is allowed a fall-through to 0 stays 0.  A row with no mask and no bias is untouched:
+ * its outputs are bit for bit those of l2_step_batch / l2_step_batch_logprobs; caches and next positions always are.
+ *   masks        n_masks bit sets of W = ceil(vocab_size / 32) words each: token j is bit j & 31 of word j >> 5; bits at or above
+ *                vocab_size in the last word are ignored.  0 <= n_masks <= n.
+ *   mask_of_row  [n], each in [-1, n_masks): the row's mask, -1 for none; several rows may name one mask.  NULL: no row is masked
+ *                (n_masks must be 0, masks is ignored).
+ *   bias_count   [n], each in [0, 256]; the rows' (id, value) pairs lie back to back in row order in bias_ids / bias_vals.  NULL: no
+ *                bias.
+ * Indices follow the call's rows.  L2_E_ARG, nothing written, in addition to l2_step_batch's rules: an index outside its range;
+ * n_masks > 0 or a non-null mask_of_row with null masks; a mask that some row names and that allows no token below vocab_size; a
+ * bias id outside [0, vocab_size) or repeated within a row; a non-finite bias value (a ban is the mask's job); a non-zero bias_count
+ * with a null id or value array; a masked row with a negative temperature (-inf / T would become +inf).  The options, the
+ * L2_SAMPLER_FORCE_SERIAL test hook and the L2_OPT_BATCH_SAMPLED_* counters behave as in l2_step_batch.
+ * Joined the surface without a version step: a binding detects it by its symbol. */
+int l2_step_batch_constrained(l2_ctx* ctx, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
+                              const double* temperature, const double* topp, uint64_t* rng_state, int32_t* picks_out, float* logits_out,
+                              int top_k, double* pick_lp_out, int32_t* top_ids_out, double* top_lp_out,
+                              const int32_t* mask_of_row, int n_masks, const uint32_t* masks,
+                              const int32_t* bias_count, const int32_t* bias_ids, const float* bias_vals);
 /* Read sequence `seq`'s key / value cache (which = L2_S_KEY_CACHE / L2_S_VALUE_CACHE; layer -1 = all), like l2_read_state. */
 int l2_read_seq_cache(l2_ctx* ctx, int seq, int which, int layer, float* out, size_t n_floats);
 /* KV-cache prefix reuse.  Copy cache rows 0 .. n_pos-1 (every layer, keys and values) of sequence `src` into the n_dst sequences

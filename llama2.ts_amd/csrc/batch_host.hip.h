@@ -1,5 +1,6 @@
 // batch_host.hip.h -- host side of batched decode (batch.hip.h): l2_seq_reserve, l2_seq_prefill, l2_seq_prefill_batch, l2_forward_batch,
-// l2_decode_greedy_batch, l2_decode_sample_batch, l2_step_batch, l2_seq_score_batch, l2_step_batch_logprobs, l2_read_seq_cache, l2_seq_fork.
+// l2_decode_greedy_batch, l2_decode_sample_batch, l2_step_batch, l2_seq_score_batch, l2_step_batch_logprobs, l2_step_batch_constrained,
+// l2_read_seq_cache, l2_seq_fork.
 // The batch step (bt_forward) and the packed launch sequences (bp_enqueue) are prefill_host.hip.h's pf_layers with row tables, their own
 // activation sets and attention; what they share -- argument checks, the row classifier, the decode-form attention, the row sampler's
 // staging and read-back -- is one helper each, here.
@@ -36,6 +37,9 @@ struct BatchState {
   float* slogits = nullptr;               // [BP_ROWS][V]: the logits of every row of one packed launch sequence (l2_seq_score_batch)
   char* lpbuf = nullptr;                  // device: a call's targets and outputs (lp_bufs' layout), lpbuf_cap bytes
   size_t lpbuf_cap = 0;
+  // Constrained picks (constrain.hip.h), allocated at the first call that carries a mask or a bias list
+  unsigned* csbuf = nullptr;              // device: a call's row tables, masks and bias pairs (cs_tables' layout), csbuf_cap words
+  size_t csbuf_cap = 0;
   int* seq_of() const { return tab; }
   int* tok_of() const { return tab + BT_MAX; }
   int* pos_of() const { return tab + 2 * BT_MAX; }
@@ -53,7 +57,7 @@ static void batch_free(l2_ctx* c) {
   bt_drop_graphs(b);
   for (size_t s = 1; s < b->kc.size(); ++s) { if (b->kc[s]) hipFree(b->kc[s]); if (b->vc[s]) hipFree(b->vc[s]); }
   void* dev[] = {b->d_kc, b->d_vc, b->tab, b->out, b->act.x, b->act.xn, b->act.q, b->act.xb, b->act.hb, b->logits, b->pact.x, b->pact.xn, b->pact.q,
-                 b->pact.xb, b->pact.hb, b->ptab, b->slogits, b->lpbuf};
+                 b->pact.xb, b->pact.hb, b->ptab, b->slogits, b->lpbuf, b->csbuf};
   for (void* p : dev) if (p) hipFree(p);
   if (b->h_tab) hipHostFree(b->h_tab);
   if (b->smp) { l2s::destroy_rows(b->smp); delete b->smp; }
@@ -674,15 +678,95 @@ extern "C" int l2_seq_score_batch(l2_ctx* c, int n, const int32_t* seqs, const i
   return L2_OK;
 }
 
-// ---- the mixed step (l2_step_batch, l2_step_batch_logprobs) ---------------------------------------
+// ---- constraints of the mixed step (l2_step_batch_constrained; kernels: constrain.hip.h) -----------
+// The constraint arguments of a call, in call order (l2_step_batch_constrained; its context-free checks are cs_check_free).
+struct BtConstraint {
+  const int32_t* mask_of_row; int n_masks; const uint32_t* masks;
+  const int32_t* bias_count; const int32_t* bias_ids; const float* bias_vals;
+};
+
+// What needs no context: n (so that the arrays can be walked), the null combinations, n_masks, every row's mask index and bias count,
+// the bias values.
+static int cs_check_free(int n, const BtConstraint& k) {
+  if (n < 1 || n > BT_MAX) return fail(L2_E_ARG, "n = %d outside [1, %d]", n, (int)BT_MAX);
+  if (k.n_masks < 0 || k.n_masks > n) return fail(L2_E_ARG, "n_masks %d outside [0, n = %d]", k.n_masks, n);
+  if (!k.mask_of_row && k.n_masks != 0) return fail(L2_E_ARG, "n_masks %d with a null mask_of_row", k.n_masks);
+  if ((k.n_masks > 0 || k.mask_of_row) && !k.masks) return fail(L2_E_ARG, "null masks");
+  for (int i = 0; k.mask_of_row && i < n; ++i)
+    if (k.mask_of_row[i] < -1 || k.mask_of_row[i] >= k.n_masks) return fail(L2_E_ARG, "row %d: mask %d outside [-1, n_masks = %d)", i, k.mask_of_row[i], k.n_masks);
+  size_t nb = 0;
+  for (int i = 0; k.bias_count && i < n; ++i) {
+    if (k.bias_count[i] < 0 || k.bias_count[i] > CS_BIAS_MAX) return fail(L2_E_ARG, "row %d: bias_count %d outside [0, %d]", i, k.bias_count[i], (int)CS_BIAS_MAX);
+    nb += (size_t)k.bias_count[i];
+  }
+  if (nb > 0 && (!k.bias_ids || !k.bias_vals)) return fail(L2_E_ARG, "bias_count names %zu entries, null bias_ids / bias_vals", nb);
+  for (size_t j = 0; j < nb; ++j)
+    if (!(fabsf(k.bias_vals[j]) < INFINITY)) return fail(L2_E_ARG, "bias value %zu is not finite (a ban is the mask's job)", j);
+  return L2_OK;
+}
+
+// What needs V: a mask some row names allows a token below V, every bias id lies in [0, V) and appears once in its row, no masked row
+// has a negative temperature (-inf / T would become +inf).
+static int cs_check_vocab(const l2_ctx* c, int n, const BtConstraint& k, const double* temperature) {
+  const int V = c->V, W = (V + 31) / 32;
+  for (int i = 0; k.mask_of_row && i < n; ++i) {
+    const int m = k.mask_of_row[i];
+    if (m < 0) continue;
+    const uint32_t* w = k.masks + (size_t)m * W;
+    bool some = false;
+    for (int q = 0; q < W && !some; ++q) some = (q == W - 1 && (V & 31) ? w[q] & ((1u << (V & 31)) - 1u) : w[q]) != 0;
+    if (!some) return fail(L2_E_ARG, "row %d: mask %d allows no token below vocab_size=%d", i, m, V);
+    if (temperature && temperature[i] < 0.0) return fail(L2_E_ARG, "row %d: a masked row with temperature %g < 0", i, temperature[i]);
+  }
+  size_t off = 0;
+  for (int i = 0; k.bias_count && i < n; off += (size_t)k.bias_count[i], ++i) {
+    const int32_t* ids = k.bias_ids + off;
+    for (int j = 0; j < k.bias_count[i]; ++j) {
+      if (ids[j] < 0 || ids[j] >= V) return fail(L2_E_ARG, "row %d: bias id %d outside [0, vocab_size=%d)", i, ids[j], V);
+      for (int q = 0; q < j; ++q) if (ids[q] == ids[j]) return fail(L2_E_ARG, "row %d: bias id %d appears twice", i, ids[j]);
+    }
+  }
+  return L2_OK;
+}
+
+// The call's device tables (constrain.hip.h: their layout) for rows in packing order `ord`, staged in `h`: kept by the caller until
+// the stream has been synchronised.  *nb_out: the bias entries of the call.
+static void cs_tables(const l2_ctx* c, int n, const BtConstraint& k, const int* ord, std::vector<uint32_t>& h, size_t* nb_out) {
+  const size_t W = (size_t)(c->V + 31) / 32, mw = (size_t)k.n_masks * W;
+  std::vector<size_t> off(n + 1, 0);      // the rows' lists lie back to back in call order
+  for (int i = 0; i < n; ++i) off[i + 1] = off[i] + (size_t)(k.bias_count ? k.bias_count[i] : 0);
+  const size_t nb = off[n];
+  h.assign(3 * (size_t)n + mw + 2 * nb, 0u);
+  size_t at = 0;                          // ... and in packing order on the device
+  for (int j = 0; j < n; ++j) {
+    const int i = ord[j], cnt = k.bias_count ? k.bias_count[i] : 0;
+    h[j] = (uint32_t)(k.mask_of_row ? k.mask_of_row[i] : -1);
+    h[n + j] = (uint32_t)at;
+    h[2 * n + j] = (uint32_t)cnt;
+    if (cnt) {
+      memcpy(h.data() + 3 * n + mw + at, k.bias_ids + off[i], (size_t)cnt * 4);
+      memcpy(h.data() + 3 * n + mw + nb + at, k.bias_vals + off[i], (size_t)cnt * 4);
+    }
+    at += (size_t)cnt;
+  }
+  if (mw) memcpy(h.data() + 3 * n, k.masks, mw * 4);
+  *nb_out = nb;
+}
+
+// ---- the mixed step (l2_step_batch, l2_step_batch_logprobs, l2_step_batch_constrained) ------------
 // The runs are reordered so that the one-row runs (decode rows) come first, then packed and run as above; every run's last-position
 // logits then get one pick on the device: bt_argmax_kernel when no row samples, else the row sampler's phases and bt_pick_kernel.  The
 // picks land in the batch step's token table (its position and start columns zeroed first, so each row's pick is also out[r][0]); only
 // they, the rng states and the optional logits come back.  With pick_lp_out (l2_step_batch_logprobs), lp_rows_kernel then reads the
 // picks from that table as its targets and the unscaled logits rows; without it the step enqueues nothing more.
+// With constraints (l2_step_batch_constrained) two launches join that sequence, and only when a row needs them: bt_constrain_rows_kernel
+// rewrites the masked and biased rows of b->logits right after the classifier, so the sampler, the pick, lp_rows_kernel and the logits
+// copy all see the constrained rows; bt_allowed_pick_kernel, after the pick, replaces a sampled pick that its row's mask forbids (the
+// reference's `return 0`) by the row's first maximum.
+
 static int bt_step(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
                    const double* temperature, const double* topp, uint64_t* rng_state, int32_t* picks_out, float* logits_out,
-                   int top_k, double* pick_lp_out, int32_t* top_ids_out, double* top_lp_out) {
+                   int top_k, double* pick_lp_out, int32_t* top_ids_out, double* top_lp_out, const BtConstraint* cs = nullptr) {
   size_t R = 0;
   int rc = bp_check(c, n, seqs, n_tokens, tokens, pos0, &R);
   if (rc) return rc;
@@ -693,6 +777,16 @@ static int bt_step(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_token
   rc = bt_check_sampling(c, n, temperature, topp, &any);
   if (rc) return rc;
   if (top_k > c->V) return fail(L2_E_ARG, "top_k %d > vocab_size %d", top_k, c->V);
+  bool constrain = false, redo = false;      // some row has a mask or a bias list; some row samples under a mask
+  if (cs) {
+    rc = cs_check_vocab(c, n, *cs, temperature);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i) {
+      const bool masked = cs->mask_of_row && cs->mask_of_row[i] >= 0;
+      constrain = constrain || masked || (cs->bias_count && cs->bias_count[i] > 0);
+      redo = redo || (masked && temperature && temperature[i] != 0.0);
+    }
+  }
 
   // packing order: decode rows (runs of one row) first, then the longer runs, each group in call order
   std::vector<int> ord;
@@ -726,14 +820,43 @@ static int bt_step(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_token
     rc = lp_bufs(c, (size_t)n, top_k, o);
     if (rc) return rc;
   }
+  std::vector<uint32_t> cstab;      // the constraint tables as uploaded: kept until the stream has been synchronised
+  size_t cs_nb = 0;
+  if (constrain) {
+    cs_tables(c, n, *cs, ord.data(), cstab, &cs_nb);
+    if (cstab.size() > b->csbuf_cap) {
+      HIPCHK(hipStreamSynchronize(st));
+      if (b->csbuf) { HIPCHK(hipFree(b->csbuf)); b->csbuf = nullptr; b->csbuf_cap = 0; }
+      HIPCHK(hipMalloc(&b->csbuf, cstab.size() * sizeof(uint32_t)));
+      b->csbuf_cap = cstab.size();
+    }
+  }
   HIPCHK(hipStreamSynchronize(st));      // (the pinned tables: the previous call's copies have completed)
   BpPlan plan;
   rc = bp_enqueue(c, n, ps.data(), pn.data(), ptok.data(), pp.data(), R, nd, true, plan);
   if (rc) return rc;
+  const int csW = (c->V + 31) / 32;
+  const int* cs_mask_of = nullptr;
+  const unsigned* cs_masks = nullptr;
+  if (constrain) {      // the masked and biased rows of b->logits, rewritten before anything reads them
+    cs_mask_of = reinterpret_cast<const int*>(b->csbuf);
+    cs_masks = b->csbuf + 3 * (size_t)n;
+    HIPCHK(hipMemcpyAsync(b->csbuf, cstab.data(), cstab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    const unsigned* bias = cs_masks + (size_t)cs->n_masks * csW;
+    const ConstrainArgs ca = {b->logits, cs_mask_of, cs_mask_of + n, cs_mask_of + 2 * n, cs_masks, reinterpret_cast<const int*>(bias),
+                              reinterpret_cast<const float*>(bias + cs_nb), c->V, csW};
+    hipLaunchKernelGGL(bt_constrain_rows_kernel, dim3((c->V + CS_COLS - 1) / CS_COLS, n), dim3(CS_THREADS), 0, st, ca);
+    LCHK(hipGetLastError());
+  }
   HIPCHK(hipMemsetAsync(b->tab, 0, 4 * BT_MAX * sizeof(int), st));
   if (any) { rc = bt_sampler_upload(*b->smp, n, {temperature, topp, rng_state}, ord.data(), st); if (rc) return rc; }
   rc = bt_enqueue_pick(c, n, any, st);
   if (rc) return rc;
+  if (redo) {      // a sampled pick its row's mask forbids becomes the row's first maximum
+    const AllowedPickArgs pa = {b->logits, b->smp->params, cs_mask_of, cs_masks, b->tok_of(), b->out, c->V, csW, c->S};
+    hipLaunchKernelGGL(bt_allowed_pick_kernel, dim3(n), dim3(1024), 0, st, pa);
+    LCHK(hipGetLastError());
+  }
   std::vector<char> lpbytes;
   if (pick_lp_out) {      // after the pick: its log-probability under the unscaled logits, and the top-k
     LCHK(launch_lp_rows(c, b->logits, n, b->tok_of(), o, 0, top_k, st));
@@ -779,6 +902,20 @@ extern "C" int l2_step_batch_logprobs(l2_ctx* c, int n, const int32_t* seqs, con
   const int rc = lp_check_k(top_k, top_ids_out, top_lp_out);
   if (rc) return rc;
   return bt_step(c, n, seqs, n_tokens, tokens, pos0, temperature, topp, rng_state, picks_out, logits_out, top_k, pick_lp_out, top_ids_out, top_lp_out);
+}
+
+extern "C" int l2_step_batch_constrained(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
+                                         const double* temperature, const double* topp, uint64_t* rng_state, int32_t* picks_out, float* logits_out,
+                                         int top_k, double* pick_lp_out, int32_t* top_ids_out, double* top_lp_out,
+                                         const int32_t* mask_of_row, int n_masks, const uint32_t* masks,
+                                         const int32_t* bias_count, const int32_t* bias_ids, const float* bias_vals) {
+  if (!pick_lp_out && top_k != 0) return fail(L2_E_ARG, "top_k %d with a null pick_lp_out", top_k);
+  int rc = pick_lp_out ? lp_check_k(top_k, top_ids_out, top_lp_out) : L2_OK;
+  if (rc) return rc;
+  const BtConstraint cs = {mask_of_row, n_masks, masks, bias_count, bias_ids, bias_vals};
+  rc = cs_check_free(n, cs);
+  if (rc) return rc;
+  return bt_step(c, n, seqs, n_tokens, tokens, pos0, temperature, topp, rng_state, picks_out, logits_out, top_k, pick_lp_out, top_ids_out, top_lp_out, &cs);
 }
 
 extern "C" int l2_read_seq_cache(l2_ctx* c, int seq, int which, int layer, float* out, size_t n_floats) {

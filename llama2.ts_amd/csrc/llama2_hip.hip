@@ -35,6 +35,7 @@
 #include "batch.hip.h"
 #include "fork.hip.h"
 #include "logprob.hip.h"
+#include "constrain.hip.h"
 #include "sampler.h"
 #include "aql_queue.h"
 

@@ -39,7 +39,7 @@ ABI_SYMBOLS = ["l2_abi_version", "l2_device_count", "l2_last_error", "l2_create"
                "l2_timer_stop", "l2_bench_gemv", "l2_bench_decode", "l2_load_checkpoint", "l2_get_header", "l2_prefill", "l2_bench_dominant_in_situ", "l2_tp_mode", "l2_create_ex", "l2_bench_tokens", "l2_dispatch_reason",
                "l2_seq_reserve", "l2_seq_prefill", "l2_forward_batch", "l2_decode_greedy_batch", "l2_read_seq_cache",
                "l2_decode_sample_batch", "l2_seq_prefill_batch", "l2_step_batch", "l2_seq_score_batch", "l2_step_batch_logprobs",
-               "l2_seq_fork"]
+               "l2_seq_fork", "l2_step_batch_constrained"]
 
 
 class L2Error(RuntimeError):
@@ -105,6 +105,7 @@ def lib():
     L.l2_seq_score_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     L.l2_step_batch_logprobs.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     L.l2_seq_fork.argtypes = [vp, i32, i32, vp, i32]
+    L.l2_step_batch_constrained.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     for name in ABI_SYMBOLS:   # fail at load time, not at first use, if the .so is stale
         getattr(L, name)
     _lib = L
@@ -127,6 +128,27 @@ class Config:
         self.vocab_size = abs(vocab)
         self.shared_weights = vocab > 0
         self.head_size = self.dim // self.n_heads
+
+
+def pack_mask(allowed, V):
+    """A token mask of l2_step_batch_constrained as uint32[ceil(V / 32)]: token j is bit j & 31 of word j >> 5.  `allowed`: an iterable
+    of ids in [0, V), or a bool array of V entries."""
+    V = int(V)
+    a = np.asarray(allowed if isinstance(allowed, np.ndarray) else list(allowed))
+    W = (V + 31) // 32
+    bits = np.zeros(32 * W, dtype=bool)
+    if a.dtype == np.bool_:
+        if a.shape != (V,):
+            raise ValueError("a bool mask needs exactly vocab_size = %d entries" % V)
+        bits[:V] = a
+    elif a.size:
+        if a.dtype.kind not in "iu":
+            raise ValueError("token ids must be integers")
+        ids = a.reshape(-1).astype(np.int64)
+        if ids.min() < 0 or ids.max() >= V:
+            raise ValueError("token id outside [0, vocab_size = %d)" % V)
+        bits[ids] = True
+    return np.packbits(bits, bitorder="little").view("<u4").astype(np.uint32)
 
 
 def running_sums(values, device=0):
@@ -300,12 +322,15 @@ class Context:
                                         tlp.ctypes.data if k > 0 else None))
         return lp, am, ids, tlp
 
-    def step_batch(self, seqs, runs, pos0, temperature=0.0, topp=1.0, rng=None, logits=False, logprobs=None):
+    def step_batch(self, seqs, runs, pos0, temperature=0.0, topp=1.0, rng=None, logits=False, logprobs=None, allowed=None, logit_bias=None):
         """One mixed step: feed runs[i] into sequence seqs[i] at pos0[i].. (a run of one token is a decode row), then one pick per row
         from its run's last-position logits, made on the device (temperature 0: argmax, no draw; else one xorshift* draw from rng[i]).
         temperature / topp: a scalar or one per row; rng: one state per row (uint64), or None when every row is greedy.  Returns
         (picks, rng_after[, (n, V) logits the picks were made from]).  logprobs = k (0 .. 20) also returns (pick_lp, top_ids, top_lp):
-        each pick's fp64 log-probability under the unscaled logits, and the k largest logits' ids / lps per row ((n, k) arrays)."""
+        each pick's fp64 log-probability under the unscaled logits, and the k largest logits' ids / lps per row ((n, k) arrays).
+        allowed: None, or per row None / an iterable of ids / a bool array of V -- the only tokens the row may pick; logit_bias: None,
+        or per row None / a {id: value} dict added to those logits (l2_step_batch_constrained: the pick, the returned logits and the
+        log-probabilities are all those of the constrained row).  Identical masks are uploaded once."""
         s = np.ascontiguousarray(seqs, dtype=np.int32).reshape(-1)
         n = s.size
         rs = [np.ascontiguousarray(r, dtype=np.int32).reshape(-1) for r in runs]
@@ -327,6 +352,19 @@ class Context:
             if st.size != n:
                 raise ValueError("one rng state per row")
         ptr = lambda a: None if a is None else a.ctypes.data
+        if allowed is not None or logit_bias is not None:
+            k = 0 if logprobs is None else int(logprobs)
+            plp = None if logprobs is None else np.empty(n, dtype=np.float64)
+            ids = np.empty((n, max(k, 0)), dtype=np.int32)
+            tlp = np.empty((n, max(k, 0)), dtype=np.float64)
+            mask_of, masks, bcount, bids, bvals = self._constraints(n, allowed, logit_bias)
+            _check(lib().l2_step_batch_constrained(self._h, n, s.ctypes.data, nt.ctypes.data, tok.ctypes.data, p0.ctypes.data,
+                                                   None if st is None else temp.ctypes.data, None if st is None else tp.ctypes.data, ptr(st),
+                                                   picks.ctypes.data, ptr(out), k, ptr(plp), ids.ctypes.data if k > 0 else None,
+                                                   tlp.ctypes.data if k > 0 else None, ptr(mask_of), 0 if masks is None else len(masks),
+                                                   ptr(masks), ptr(bcount), ptr(bids), ptr(bvals)))
+            after = None if st is None else [int(v) for v in st]
+            return (picks.tolist(), after) + ((out,) if logits else ()) + (((plp, ids, tlp),) if logprobs is not None else ())
         if logprobs is None:
             _check(lib().l2_step_batch(self._h, n, s.ctypes.data, nt.ctypes.data, tok.ctypes.data, p0.ctypes.data,
                                        None if st is None else temp.ctypes.data, None if st is None else tp.ctypes.data, ptr(st),
@@ -343,6 +381,37 @@ class Context:
                                             tlp.ctypes.data if k > 0 else None))
         after = None if st is None else [int(v) for v in st]
         return (picks.tolist(), after) + ((out,) if logits else ()) + ((plp, ids, tlp),)
+
+    def _constraints(self, n, allowed, logit_bias):
+        """The constraint arrays of l2_step_batch_constrained for n rows: (mask_of_row, masks (m, W), bias_count, bias_ids, bias_vals),
+        None where the call takes NULL.  Masks are deduplicated by their packed bytes."""
+        mask_of = masks = bcount = bids = bvals = None
+        if allowed is not None:
+            allowed = list(allowed)
+            if len(allowed) != n:
+                raise ValueError("one allowed entry per row")
+            if any(a is not None for a in allowed):
+                mask_of = np.full(n, -1, dtype=np.int32)
+                seen, packed = {}, []
+                for i, a in enumerate(allowed):
+                    if a is None:
+                        continue
+                    m = pack_mask(a, self.cfg.vocab_size)
+                    key = m.tobytes()
+                    if key not in seen:
+                        seen[key] = len(packed)
+                        packed.append(m)
+                    mask_of[i] = seen[key]
+                masks = np.ascontiguousarray(np.stack(packed), dtype=np.uint32)
+        if logit_bias is not None:
+            logit_bias = list(logit_bias)
+            if len(logit_bias) != n:
+                raise ValueError("one logit_bias entry per row")
+            if any(logit_bias):
+                bcount = np.array([len(b) if b else 0 for b in logit_bias], dtype=np.int32)
+                bids = np.array([int(t) for b in logit_bias if b for t in b.keys()], dtype=np.int32)
+                bvals = np.array([float(v) for b in logit_bias if b for v in b.values()], dtype=np.float32)
+        return mask_of, masks, bcount, bids, bvals
 
     @staticmethod
     def _rows(*cols):

@@ -17,6 +17,13 @@ A request submitted with logprobs=k (0 .. 20) gets, for each of its picks (the B
 model's unscaled logits and the k most likely tokens with theirs, in Result.logprobs.  Only a step that holds such a request calls the
 logprobs form of the step (l2_step_batch_logprobs), which leaves picks, rng states and caches exactly as the plain step does.
 
+A request queued by submit_constrained or submit_n with allowed= and / or logit_bias= has every one of its picks constrained
+(include/llama2_hip.h: l2_step_batch_constrained): `allowed` is an iterable of token ids (the same set for every pick) or a callable f(tokens_fed) -> iterable
+of ids, or None for "anything" -- called once per real pick with every token of the request fed up to and including that step's, the
+context the pick continues; `logit_bias` is a {id: value} dict added to the logits of every pick.  Picks, kept logits and logprobs are
+those of the constrained rows.  A constrained pick of BOS still ends the request: allowing BOS is how a grammar says "may stop here".
+A prompt chunk whose pick is thrown away is never constrained.  The keywords reach ctx.step_batch only in a step with such a pick.
+
 Scheduler(ctx, ..., prefix_cache=True) does not feed a prompt prefix whose cache rows the device already holds (a cache row of position
 p depends on tokens 0 .. p only).  The scheduler remembers per slot the tokens whose rows it holds (`resident`: what was fed since the
 slot's last restart; a finished request's rows stay until the slot is restarted).  A request with known tokens K = [BOS] + prompt may
@@ -51,7 +58,7 @@ class Result:
 
 
 class _Request:
-    def __init__(self, rid, prompt, steps, temperature, topp, seed, logprobs=None):
+    def __init__(self, rid, prompt, steps, temperature, topp, seed, logprobs=None, allowed=None, logit_bias=None):
         self.rid = rid
         stop = prompt.index(BOS) if BOS in prompt else -1      # a forced BOS ends the reference's loop there (llama2.ts:497)
         self.prompt = prompt if stop < 0 else prompt[:stop]
@@ -64,6 +71,8 @@ class _Request:
         self.logits = []
         self.top = None if logprobs is None else int(logprobs)
         self.logprobs = []
+        self.allowed = allowed if allowed is None or callable(allowed) else [int(t) for t in allowed]
+        self.logit_bias = dict(logit_bias) if logit_bias else None
         self.leader = None                      # submit_n with prefix_cache: the sample that feeds the prompt this one waits for
         self.done = False
 
@@ -120,20 +129,26 @@ class Scheduler:
         0 .. 20 -- the log-probability of each pick and the k most likely tokens' (Result.logprobs)."""
         return self._submit(prompt_ids, steps, temperature, topp, seed, logprobs).rid
 
-    def submit_n(self, prompt_ids, steps, seeds, temperature=0.0, topp=1.0, logprobs=None):
+    def submit_constrained(self, prompt_ids, steps, temperature=0.0, topp=1.0, seed=1, logprobs=None, allowed=None, logit_bias=None):
+        """submit() with constraints on every pick of the request (submit's own parameter list is pinned by tests/test_fork_cpu.py).
+        allowed: None, an iterable of ids, or a callable f(tokens_fed) -> iterable of ids or None; logit_bias: None or {id: value}
+        (see the module's text)."""
+        return self._submit(prompt_ids, steps, temperature, topp, seed, logprobs, allowed, logit_bias).rid
+
+    def submit_n(self, prompt_ids, steps, seeds, temperature=0.0, topp=1.0, logprobs=None, allowed=None, logit_bias=None):
         """Queue len(seeds) samples of one prompt, each a request of its own with its own rng state; returns their ids.  With
         prefix_cache the first is admitted as any request; the others become admissible once its prompt rows are resident (all of
         [BOS] + prompt but the last token) and take them by one fork.  Once the first has fed its prompt they are ordinary waiting
         requests: if its rows are gone when a slot comes free, they feed the prompt themselves."""
         reqs = []
         for seed in seeds:
-            r = self._submit(prompt_ids, steps, temperature, topp, seed, logprobs)
+            r = self._submit(prompt_ids, steps, temperature, topp, seed, logprobs, allowed, logit_bias)
             if reqs and self.prefix_cache:
                 r.leader = reqs[0]
             reqs.append(r)
         return [r.rid for r in reqs]
 
-    def _submit(self, prompt_ids, steps, temperature, topp, seed, logprobs):
+    def _submit(self, prompt_ids, steps, temperature, topp, seed, logprobs, allowed=None, logit_bias=None):
         steps = int(steps)
         if steps < 0 or steps > self.seq_len:
             raise ValueError("steps %d outside [0, seq_len=%d]" % (steps, self.seq_len))
@@ -141,7 +156,7 @@ class Scheduler:
             raise ValueError("temperature / topp is NaN")
         if logprobs is not None and not 0 <= int(logprobs) <= 20:
             raise ValueError("logprobs %d outside [0, 20]" % int(logprobs))
-        r = _Request(self._next_id, [int(t) for t in prompt_ids], steps, temperature, topp, seed, logprobs)
+        r = _Request(self._next_id, [int(t) for t in prompt_ids], steps, temperature, topp, seed, logprobs, allowed, logit_bias)
         self._next_id += 1
         self.waiting.append(r)
         return r
@@ -248,6 +263,13 @@ class Scheduler:
         rng = [r.rng for r, _, _, _ in rows]
         ks = [r.top for r, _, _, _ in rows if r.top is not None]
         extra = {"logprobs": max(ks)} if ks else {}
+        # constraints of the real picks (a callable sees the tokens fed up to and including this step's); a thrown-away pick has none
+        masks = [(r.allowed(r.fed + t) if callable(r.allowed) else r.allowed) if real else None for r, t, _, real in rows]
+        bias = [r.logit_bias if real else None for r, _, _, real in rows]
+        if any(m is not None for m in masks):
+            extra["allowed"] = masks
+        if any(b is not None for b in bias):
+            extra["logit_bias"] = bias
         out = self.ctx.step_batch(seqs, [t for _, t, _, _ in rows], [p for _, _, p, _ in rows], temperature=temp, topp=topp, rng=rng,
                                   logits=self.keep_logits, **extra)
         self.calls += 1
