@@ -29,7 +29,7 @@ extern "C" {
  * version step: it only adds, and a binding detects it by the presence of the l2_seq_reserve symbol.  So did its sampled loop
  * (l2_decode_sample_batch, option keys L2_OPT_BATCH_SAMPLED_TOKENS / _SERIAL), detected by its own symbol, and so were the packed
  * prompts (l2_seq_prefill_batch) and the mixed step (l2_step_batch), the per-token log-probabilities (l2_seq_score_batch,
- * l2_step_batch_logprobs), constrained picks (l2_step_batch_constrained), and so is the cache prefix copy (its one call is declared
+ * l2_step_batch_logprobs), constrained picks (l2_step_batch_constrained), sampling controls (l2_step_batch_sampling), and so is the cache prefix copy (its one call is declared
  * below, beside the cache read). */
 #define L2_ABI_VERSION 5
 
@@ -320,6 +320,58 @@ int l2_step_batch_constrained(l2_ctx* ctx, int n, const int32_t* seqs, const int
                               int top_k, double* pick_lp_out, int32_t* top_ids_out, double* top_lp_out,
                               const int32_t* mask_of_row, int n_masks, const uint32_t* masks,
                               const int32_t* bias_count, const int32_t* bias_ids, const float* bias_vals);
+/* Sampling controls of a mixed step's rows: penalties on tokens already seen, top-k and min-p.  Every array follows the call's rows;
+ * a NULL array switches its control off for every row.
+ *   hist_count / hist_ids      row i's history: hist_count[i] token ids, the rows' lists back to back in row order.  c_j = how often
+ *                              id j occurs in it.
+ *   repetition, presence, frequency   STAGE A, visible.  For every j with c_j > 0, before the bias and the mask of the row:
+ *       y     = rep == 1 ? x[j] : (x[j] > 0 ? (float)((double)x[j] / rep) : (float)((double)x[j] * rep))
+ *       x'[j] = presence == 0 && frequency == 0 ? y : (float)((double)y - (presence + frequency * (double)c_j))
+ *     each operation rounded on its own; an id with c_j == 0 is not written (bit for bit); -inf and NaN come out as the formula gives
+ *     them.  The argmax, the sampler, logits_out, pick_lp_out and the top lists all see the penalised, then constrained row x'.
+ *   sample_top_k, min_p        STAGE B, sampler-only, like top-p: for a row with temperature > 0 the row sampler reads
+ *       x''[j] = x'[j]   fewer than sample_top_k ids rank before j (descending value, equal values by ascending id: the order of
+ *                        the top lists; sample_top_k >= vocab_size truncates nothing) AND
+ *                        (double)s_j - (double)s_max >= log(min_p), s_j = (float)((double)x'[j] / T), s_max its row maximum
+ *       x''[j] = -inf    otherwise
+ *     while logits_out, pick_lp_out and the top lists keep reading x'.  Top-p then acts on the renormalised survivors inside the
+ *     unchanged sampler.  A greedy row ignores stage B.  If the sampler's pick is an id with x'' = -inf -- only the `return 0` of
+ *     llama2.ts:375 / :393 can be, e.g. every time for sample_top_k = 1 under 0 < topp < 1 -- the pick is the first maximum of x''
+ *     (llama2.ts:364-366); the draw has still been made and rng_state[i] is what the reference would leave. */
+typedef struct l2_sample_controls {
+  const int32_t* hist_count;    /* [n] each in [0, seq_len]; NULL: no row has a history */
+  const int32_t* hist_ids;      /* the rows' histories back to back in row order, ids in [0, vocab_size) */
+  const double* repetition;     /* [n] > 0 and finite, 1 = off; NULL: all 1 */
+  const double* presence;       /* [n] finite; NULL: all 0 */
+  const double* frequency;      /* [n] finite; NULL: all 0 */
+  const int32_t* sample_top_k;  /* [n] >= 0, 0 = off; NULL: off */
+  const double* min_p;          /* [n] in [0, 1], 0 = off; NULL: off */
+} l2_sample_controls;
+/* l2_step_batch_constrained with sampling controls: every parameter of that call, in its order, then `sc`.  sc == NULL is exactly
+ * l2_step_batch_constrained; a row with no history (or repetition 1, presence 0, frequency 0), sample_top_k 0 and min_p 0 is
+ * untouched: its outputs are bit for bit those of that call.  Caches, next positions, the options and the
+ * L2_OPT_BATCH_SAMPLED_* counters behave as there.  Up to three launches join the step, each only when a row needs it: the
+ * penalties (before the bias / mask rewrite), the truncated copy of the rows (before the row sampler, which then reads the copy),
+ * the fall-through of the rows that truncate (after the pick; a row that is only masked keeps l2_step_batch_constrained's own rule, so
+ * no row's pick depends on what the other rows of its call ask for).
+ * L2_E_ARG, nothing written and nothing launched, in addition to that call's rules: a hist_count outside [0, seq_len]; a non-zero
+ * count with a null hist_ids; a history id outside [0, vocab_size); a repetition that is not positive and finite; a presence or
+ * frequency that is not finite; sample_top_k < 0; min_p outside [0, 1]; a NaN; a row with sample_top_k > 0 or min_p > 0 and a
+ * negative temperature.  What needs no context is checked before the context is looked at.
+ * Joined the surface without a version step: a binding detects it by its symbol. */
+int l2_step_batch_sampling(l2_ctx* ctx, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
+                           const double* temperature, const double* topp, uint64_t* rng_state, int32_t* picks_out, float* logits_out,
+                           int top_k, double* pick_lp_out, int32_t* top_ids_out, double* top_lp_out,
+                           const int32_t* mask_of_row, int n_masks, const uint32_t* masks,
+                           const int32_t* bias_count, const int32_t* bias_ids, const float* bias_vals,
+                           const l2_sample_controls* sc);
+/* Diagnostic for the two rewriting launches of the sampling controls, with no model: n_rows (1 .. 64) rows of `vocab`
+ * (1 .. the device sampler's limit) caller-supplied logits go through stage A into penalised_out and through stage B into
+ * truncated_out (each n_rows x vocab floats; either may be NULL).  temperature: [n_rows], NULL = every row greedy (stage B copies).
+ * The rules of `sc` are those of the step, with hist_count bounded by 65 536 instead of seq_len.  Synchronous; tests compare it
+ * bit for bit with a numpy statement of the rules. */
+int l2_debug_sample_controls(int device, int n_rows, int vocab, const float* logits, const double* temperature,
+                             const l2_sample_controls* sc, float* penalised_out, float* truncated_out);
 /* Read sequence `seq`'s key / value cache (which = L2_S_KEY_CACHE / L2_S_VALUE_CACHE; layer -1 = all), like l2_read_state. */
 int l2_read_seq_cache(l2_ctx* ctx, int seq, int which, int layer, float* out, size_t n_floats);
 /* KV-cache prefix reuse.  Copy cache rows 0 .. n_pos-1 (every layer, keys and values) of sequence `src` into the n_dst sequences

@@ -1,6 +1,6 @@
 // batch_host.hip.h -- host side of batched decode (batch.hip.h): l2_seq_reserve, l2_seq_prefill, l2_seq_prefill_batch, l2_forward_batch,
 // l2_decode_greedy_batch, l2_decode_sample_batch, l2_step_batch, l2_seq_score_batch, l2_step_batch_logprobs, l2_step_batch_constrained,
-// l2_read_seq_cache, l2_seq_fork.
+// l2_step_batch_sampling, l2_debug_sample_controls, l2_read_seq_cache, l2_seq_fork.
 // The batch step (bt_forward) and the packed launch sequences (bp_enqueue) are prefill_host.hip.h's pf_layers with row tables, their own
 // activation sets and attention; what they share -- argument checks, the row classifier, the decode-form attention, the row sampler's
 // staging and read-back -- is one helper each, here.
@@ -40,6 +40,11 @@ struct BatchState {
   // Constrained picks (constrain.hip.h), allocated at the first call that carries a mask or a bias list
   unsigned* csbuf = nullptr;              // device: a call's row tables, masks and bias pairs (cs_tables' layout), csbuf_cap words
   size_t csbuf_cap = 0;
+  // Sampling controls (controls.hip.h), allocated at the first call that penalises or truncates a row
+  char* scbuf = nullptr;                  // device: a call's control tables and history ids (sc_tables' layout), scbuf_cap bytes
+  size_t scbuf_cap = 0;
+  int* sccount = nullptr;                 // [BT_MAX][V] occurrence counts of the penalty launch: zeroed here once, left zero by every launch
+  float* tlogits = nullptr;               // [BT_MAX][V] the rows as the row sampler reads them when some row truncates (x'')
   int* seq_of() const { return tab; }
   int* tok_of() const { return tab + BT_MAX; }
   int* pos_of() const { return tab + 2 * BT_MAX; }
@@ -57,7 +62,7 @@ static void batch_free(l2_ctx* c) {
   bt_drop_graphs(b);
   for (size_t s = 1; s < b->kc.size(); ++s) { if (b->kc[s]) hipFree(b->kc[s]); if (b->vc[s]) hipFree(b->vc[s]); }
   void* dev[] = {b->d_kc, b->d_vc, b->tab, b->out, b->act.x, b->act.xn, b->act.q, b->act.xb, b->act.hb, b->logits, b->pact.x, b->pact.xn, b->pact.q,
-                 b->pact.xb, b->pact.hb, b->ptab, b->slogits, b->lpbuf, b->csbuf};
+                 b->pact.xb, b->pact.hb, b->ptab, b->slogits, b->lpbuf, b->csbuf, b->scbuf, b->sccount, b->tlogits};
   for (void* p : dev) if (p) hipFree(p);
   if (b->h_tab) hipHostFree(b->h_tab);
   if (b->smp) { l2s::destroy_rows(b->smp); delete b->smp; }
@@ -232,11 +237,12 @@ static int bt_forward(l2_ctx* c, int n, hipStream_t st) {
 }
 
 // Every row's pick from b->logits into the token table (fed next) and b->out: its argmax (llama2.ts:364-366), or -- `sampled` -- the row
-// sampler (every phase once for all n rows), then every row's pick applied.
-static int bt_enqueue_pick(l2_ctx* c, int n, bool sampled, hipStream_t st) {
+// sampler (every phase once for all n rows), then every row's pick applied.  `sampler_in`: the rows the sampler reads when they are
+// not b->logits (the truncated copy of l2_step_batch_sampling, in which a greedy row is a plain copy).
+static int bt_enqueue_pick(l2_ctx* c, int n, bool sampled, hipStream_t st, const float* sampler_in = nullptr) {
   BatchState* b = c->bt;
   if (sampled) {
-    LCHK(l2s::enqueue_rows(*b->smp, b->logits, n, l2s::PICK_BOTH, l2s::Pick{b->smp->pick, nullptr, nullptr}, st));
+    LCHK(l2s::enqueue_rows(*b->smp, sampler_in ? sampler_in : b->logits, n, l2s::PICK_BOTH, l2s::Pick{b->smp->pick, nullptr, nullptr}, st));
     hipLaunchKernelGGL(bt_pick_kernel, dim3(n), dim3(1024), 0, st, (const float*)b->logits, c->V, (const double*)b->smp->params, b->smp->pick,
                        b->tok_of(), b->pos_of(), (const int*)b->start_of(), b->out, c->S);
   } else {
@@ -753,7 +759,115 @@ static void cs_tables(const l2_ctx* c, int n, const BtConstraint& k, const int* 
   *nb_out = nb;
 }
 
-// ---- the mixed step (l2_step_batch, l2_step_batch_logprobs, l2_step_batch_constrained) ------------
+// ---- sampling controls of the mixed step (l2_step_batch_sampling; kernels: controls.hip.h) ---------
+static bool sc_finite(double v) { return fabs(v) < INFINITY; }      // false for a NaN too
+static double sc_at(const double* a, int i, double off) { return a ? a[i] : off; }
+
+// Row i has a history and a penalty that is not neutral: the penalty launch rewrites it.
+static bool sc_penalised(const l2_sample_controls& s, int i) {
+  return s.hist_count && s.hist_count[i] > 0 &&
+         (sc_at(s.repetition, i, 1.0) != 1.0 || sc_at(s.presence, i, 0.0) != 0.0 || sc_at(s.frequency, i, 0.0) != 0.0);
+}
+// Row i samples with top-k or min-p set.
+static bool sc_asks_truncation(const l2_sample_controls& s, const double* temperature, int i) {
+  return temperature && temperature[i] != 0.0 && ((s.sample_top_k && s.sample_top_k[i] > 0) || sc_at(s.min_p, i, 0.0) > 0.0);
+}
+
+// What needs no context: n (so that the arrays can be walked), every count, penalty, k and min_p, the null history, a truncating
+// row's temperature.  hist_max: the bound of a count when the caller knows it without a context (the diagnostic), else -1.
+static int sc_check_free(int n, const l2_sample_controls& s, const double* temperature, int hist_max) {
+  if (n < 1 || n > BT_MAX) return fail(L2_E_ARG, "n = %d outside [1, %d]", n, (int)BT_MAX);
+  size_t nh = 0;
+  for (int i = 0; i < n; ++i) {
+    if (s.hist_count) {
+      if (s.hist_count[i] < 0 || (hist_max >= 0 && s.hist_count[i] > hist_max))
+        return fail(L2_E_ARG, "row %d: hist_count %d outside [0, %d]", i, s.hist_count[i], hist_max >= 0 ? hist_max : INT32_MAX);
+      nh += (size_t)s.hist_count[i];
+    }
+    const double rep = sc_at(s.repetition, i, 1.0), pres = sc_at(s.presence, i, 0.0), freq = sc_at(s.frequency, i, 0.0), mp = sc_at(s.min_p, i, 0.0);
+    if (!(rep > 0.0) || !sc_finite(rep)) return fail(L2_E_ARG, "row %d: repetition %g is not positive and finite", i, rep);
+    if (!sc_finite(pres) || !sc_finite(freq)) return fail(L2_E_ARG, "row %d: presence %g / frequency %g is not finite", i, pres, freq);
+    if (s.sample_top_k && s.sample_top_k[i] < 0) return fail(L2_E_ARG, "row %d: sample_top_k %d < 0", i, s.sample_top_k[i]);
+    if (!(mp >= 0.0 && mp <= 1.0)) return fail(L2_E_ARG, "row %d: min_p %g outside [0, 1]", i, mp);
+    if (sc_asks_truncation(s, temperature, i) && temperature[i] < 0.0)
+      return fail(L2_E_ARG, "row %d: top-k / min-p with temperature %g < 0 (-inf / T would become +inf)", i, temperature[i]);
+  }
+  if (nh > 0 && !s.hist_ids) return fail(L2_E_ARG, "hist_count names %zu entries, null hist_ids", nh);
+  return L2_OK;
+}
+
+// What needs the shape: every count at most hist_max, every history id in [0, V).  This is what keeps the penalty launch in bounds.
+static int sc_check_shape(int V, int hist_max, int n, const l2_sample_controls& s) {
+  size_t off = 0;
+  for (int i = 0; s.hist_count && i < n; off += (size_t)s.hist_count[i], ++i) {
+    if (s.hist_count[i] > hist_max) return fail(L2_E_ARG, "row %d: hist_count %d outside [0, %d]", i, s.hist_count[i], hist_max);
+    for (int j = 0; j < s.hist_count[i]; ++j)
+      if (s.hist_ids[off + j] < 0 || s.hist_ids[off + j] >= V)
+        return fail(L2_E_ARG, "row %d: history id %d outside [0, vocab_size=%d)", i, s.hist_ids[off + j], V);
+  }
+  return L2_OK;
+}
+
+// The call's device tables (controls.hip.h: their layout) for rows in packing order `ord` (null: call order), staged in `h`: kept by
+// the caller until the stream has been synchronised.  Only the penalised rows' histories travel.
+struct ScPlan {
+  bool penalise = false, truncate = false;      // some row is penalised; some sampling row truncates
+  std::vector<char> h;
+  size_t ctl_off = 0, hist_off = 0;             // byte offsets of the int table and of the ids
+};
+static void sc_tables(int n, int V, const l2_sample_controls& s, const double* temperature, const int* ord, ScPlan& p) {
+  std::vector<size_t> off(n + 1, 0);
+  size_t nh = 0;
+  for (int i = 0; i < n; ++i) {
+    off[i + 1] = off[i] + (size_t)(s.hist_count ? s.hist_count[i] : 0);
+    if (sc_penalised(s, i)) nh += (size_t)s.hist_count[i];
+  }
+  p.ctl_off = 4 * (size_t)n * sizeof(double);
+  p.hist_off = p.ctl_off + 4 * (size_t)n * sizeof(int);
+  p.h.assign(p.hist_off + nh * sizeof(int), 0);
+  double* pen = reinterpret_cast<double*>(p.h.data());
+  int* ctl = reinterpret_cast<int*>(p.h.data() + p.ctl_off);
+  int* ids = reinterpret_cast<int*>(p.h.data() + p.hist_off);
+  size_t at = 0;
+  for (int j = 0; j < n; ++j) {
+    const int i = ord ? ord[j] : j;
+    const bool sampling = temperature && temperature[i] != 0.0;
+    const int k = sampling && s.sample_top_k && s.sample_top_k[i] < V ? s.sample_top_k[i] : 0;      // k >= V truncates nothing
+    const double mp = sampling ? sc_at(s.min_p, i, 0.0) : 0.0;
+    const bool tr = k > 0 || mp > 0.0;
+    pen[4 * j] = sc_at(s.repetition, i, 1.0); pen[4 * j + 1] = sc_at(s.presence, i, 0.0); pen[4 * j + 2] = sc_at(s.frequency, i, 0.0);
+    pen[4 * j + 3] = mp > 0.0 ? log(mp) : -INFINITY;
+    ctl[4 * j] = (int)at;
+    if (sc_penalised(s, i)) {
+      ctl[4 * j + 1] = s.hist_count[i];
+      memcpy(ids + at, s.hist_ids + off[i], (size_t)s.hist_count[i] * sizeof(int));
+      at += (size_t)s.hist_count[i];
+      p.penalise = true;
+    }
+    ctl[4 * j + 2] = k;
+    ctl[4 * j + 3] = tr;                                                            // the survivor rule serves the row
+    p.truncate = p.truncate || tr;
+  }
+}
+
+static ControlArgs sc_args(float* logits, float* trunc, const char* tables, const ScPlan& p, int* count, const double* params, int V) {
+  return ControlArgs{logits, trunc, reinterpret_cast<const double*>(tables), reinterpret_cast<const int*>(tables + p.ctl_off),
+                     reinterpret_cast<const int*>(tables + p.hist_off), count, params, V};
+}
+// Stage A over n rows: one launch (a.count is zero and stays so: controls.hip.h).
+static int sc_enqueue_penalties(const ControlArgs& a, int n, hipStream_t st) {
+  hipLaunchKernelGGL(bt_penalise_rows_kernel<SC_THREADS>, dim3(n), dim3(SC_THREADS), 0, st, a);
+  LCHK(hipGetLastError());
+  return L2_OK;
+}
+// Stage B: all n rows of a.trunc, from a.logits and the row sampler's settings a.params.
+static int sc_enqueue_truncation(const ControlArgs& a, int n, hipStream_t st) {
+  hipLaunchKernelGGL(bt_truncate_rows_kernel<SC_THREADS>, dim3(n), dim3(SC_THREADS), 0, st, a);
+  LCHK(hipGetLastError());
+  return L2_OK;
+}
+
+// ---- the mixed step (l2_step_batch, l2_step_batch_logprobs, l2_step_batch_constrained, l2_step_batch_sampling) ------------
 // The runs are reordered so that the one-row runs (decode rows) come first, then packed and run as above; every run's last-position
 // logits then get one pick on the device: bt_argmax_kernel when no row samples, else the row sampler's phases and bt_pick_kernel.  The
 // picks land in the batch step's token table (its position and start columns zeroed first, so each row's pick is also out[r][0]); only
@@ -763,10 +877,15 @@ static void cs_tables(const l2_ctx* c, int n, const BtConstraint& k, const int* 
 // rewrites the masked and biased rows of b->logits right after the classifier, so the sampler, the pick, lp_rows_kernel and the logits
 // copy all see the constrained rows; bt_allowed_pick_kernel, after the pick, replaces a sampled pick that its row's mask forbids (the
 // reference's `return 0`) by the row's first maximum.
+// With sampling controls (l2_step_batch_sampling) up to three more, again only when a row needs them: bt_penalise_rows_kernel before
+// the constraints' rewrite; bt_truncate_rows_kernel after the sampler's settings are up, writing the copy of the rows that the row
+// sampler then reads in place of b->logits; bt_survivor_pick_kernel after the pick for the rows that truncate, in front of
+// bt_allowed_pick_kernel, which keeps serving the masked rows.
 
 static int bt_step(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
                    const double* temperature, const double* topp, uint64_t* rng_state, int32_t* picks_out, float* logits_out,
-                   int top_k, double* pick_lp_out, int32_t* top_ids_out, double* top_lp_out, const BtConstraint* cs = nullptr) {
+                   int top_k, double* pick_lp_out, int32_t* top_ids_out, double* top_lp_out, const BtConstraint* cs = nullptr,
+                   const l2_sample_controls* sc = nullptr) {
   size_t R = 0;
   int rc = bp_check(c, n, seqs, n_tokens, tokens, pos0, &R);
   if (rc) return rc;
@@ -786,6 +905,10 @@ static int bt_step(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_token
       constrain = constrain || masked || (cs->bias_count && cs->bias_count[i] > 0);
       redo = redo || (masked && temperature && temperature[i] != 0.0);
     }
+  }
+  if (sc) {
+    rc = sc_check_shape(c->V, c->S, n, *sc);
+    if (rc) return rc;
   }
 
   // packing order: decode rows (runs of one row) first, then the longer runs, each group in call order
@@ -831,10 +954,32 @@ static int bt_step(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_token
       b->csbuf_cap = cstab.size();
     }
   }
+  ScPlan sp;                        // the control tables as uploaded: kept until the stream has been synchronised
+  if (sc) sc_tables(n, c->V, *sc, temperature, ord.data(), sp);
+  if (sp.penalise || sp.truncate) {
+    const size_t rowset = (size_t)BT_MAX * c->V;
+    if (sp.h.size() > b->scbuf_cap) {
+      HIPCHK(hipStreamSynchronize(st));
+      if (b->scbuf) { HIPCHK(hipFree(b->scbuf)); b->scbuf = nullptr; b->scbuf_cap = 0; }
+      HIPCHK(hipMalloc(&b->scbuf, sp.h.size()));
+      b->scbuf_cap = sp.h.size();
+    }
+    if (sp.penalise && !b->sccount) {
+      HIPCHK(hipMalloc(&b->sccount, rowset * sizeof(int)));
+      HIPCHK(hipMemset(b->sccount, 0, rowset * sizeof(int)));
+    }
+    if (sp.truncate && !b->tlogits) HIPCHK(hipMalloc(&b->tlogits, rowset * sizeof(float)));
+  }
   HIPCHK(hipStreamSynchronize(st));      // (the pinned tables: the previous call's copies have completed)
   BpPlan plan;
   rc = bp_enqueue(c, n, ps.data(), pn.data(), ptok.data(), pp.data(), R, nd, true, plan);
   if (rc) return rc;
+  ControlArgs xa = {};
+  if (sp.penalise || sp.truncate) {      // penalise, then add bias, then mask
+    HIPCHK(hipMemcpyAsync(b->scbuf, sp.h.data(), sp.h.size(), hipMemcpyHostToDevice, st));
+    xa = sc_args(b->logits, b->tlogits, b->scbuf, sp, b->sccount, any ? b->smp->params : nullptr, c->V);
+    if (sp.penalise) { rc = sc_enqueue_penalties(xa, n, st); if (rc) return rc; }
+  }
   const int csW = (c->V + 31) / 32;
   const int* cs_mask_of = nullptr;
   const unsigned* cs_masks = nullptr;
@@ -850,8 +995,14 @@ static int bt_step(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_token
   }
   HIPCHK(hipMemsetAsync(b->tab, 0, 4 * BT_MAX * sizeof(int), st));
   if (any) { rc = bt_sampler_upload(*b->smp, n, {temperature, topp, rng_state}, ord.data(), st); if (rc) return rc; }
-  rc = bt_enqueue_pick(c, n, any, st);
+  if (sp.truncate) { rc = sc_enqueue_truncation(xa, n, st); if (rc) return rc; }      // the rows as the sampler reads them
+  rc = bt_enqueue_pick(c, n, any, st, sp.truncate ? b->tlogits : nullptr);
   if (rc) return rc;
+  if (sp.truncate) {      // a truncating row's sampled pick that did not survive becomes the first maximum of its truncated row
+    const SurvivorPickArgs pa = {b->tlogits, xa.ctl, b->tok_of(), b->out, c->V, c->S};
+    hipLaunchKernelGGL(bt_survivor_pick_kernel<SC_THREADS>, dim3(n), dim3(SC_THREADS), 0, st, pa);
+    LCHK(hipGetLastError());
+  }
   if (redo) {      // a sampled pick its row's mask forbids becomes the row's first maximum
     const AllowedPickArgs pa = {b->logits, b->smp->params, cs_mask_of, cs_masks, b->tok_of(), b->out, c->V, csW, c->S};
     hipLaunchKernelGGL(bt_allowed_pick_kernel, dim3(n), dim3(1024), 0, st, pa);
@@ -916,6 +1067,70 @@ extern "C" int l2_step_batch_constrained(l2_ctx* c, int n, const int32_t* seqs, 
   rc = cs_check_free(n, cs);
   if (rc) return rc;
   return bt_step(c, n, seqs, n_tokens, tokens, pos0, temperature, topp, rng_state, picks_out, logits_out, top_k, pick_lp_out, top_ids_out, top_lp_out, &cs);
+}
+
+extern "C" int l2_step_batch_sampling(l2_ctx* c, int n, const int32_t* seqs, const int32_t* n_tokens, const int32_t* tokens, const int32_t* pos0,
+                                      const double* temperature, const double* topp, uint64_t* rng_state, int32_t* picks_out, float* logits_out,
+                                      int top_k, double* pick_lp_out, int32_t* top_ids_out, double* top_lp_out,
+                                      const int32_t* mask_of_row, int n_masks, const uint32_t* masks,
+                                      const int32_t* bias_count, const int32_t* bias_ids, const float* bias_vals,
+                                      const l2_sample_controls* sc) {
+  if (!pick_lp_out && top_k != 0) return fail(L2_E_ARG, "top_k %d with a null pick_lp_out", top_k);
+  int rc = pick_lp_out ? lp_check_k(top_k, top_ids_out, top_lp_out) : L2_OK;
+  if (rc) return rc;
+  const BtConstraint cs = {mask_of_row, n_masks, masks, bias_count, bias_ids, bias_vals};
+  rc = cs_check_free(n, cs);
+  if (rc) return rc;
+  if (sc) {
+    rc = sc_check_free(n, *sc, temperature, -1);
+    if (rc) return rc;
+  }
+  return bt_step(c, n, seqs, n_tokens, tokens, pos0, temperature, topp, rng_state, picks_out, logits_out, top_k, pick_lp_out, top_ids_out, top_lp_out, &cs, sc);
+}
+
+// Diagnostic: the two rewriting launches of the sampling controls on caller-supplied rows, with buffers of its own.
+extern "C" int l2_debug_sample_controls(int device, int n_rows, int vocab, const float* logits, const double* temperature,
+                                        const l2_sample_controls* sc, float* penalised_out, float* truncated_out) {
+  if (!logits || !sc) return fail(L2_E_ARG, "null logits / sc");
+  if (vocab < 1 || vocab > (int)l2s::MAX_VOCAB) return fail(L2_E_ARG, "vocab %d outside [1, %d]", vocab, (int)l2s::MAX_VOCAB);
+  int rc = sc_check_free(n_rows, *sc, temperature, SC_HIST_MAX);
+  if (rc) return rc;
+  for (int i = 0; temperature && i < n_rows; ++i)
+    if (!(temperature[i] == temperature[i])) return fail(L2_E_ARG, "row %d: temperature is NaN", i);
+  rc = sc_check_shape(vocab, SC_HIST_MAX, n_rows, *sc);
+  if (rc) return rc;
+  ScPlan sp;
+  sc_tables(n_rows, vocab, *sc, temperature, nullptr, sp);
+  std::vector<double> params(2 * (size_t)n_rows, 0.0);      // {temperature, topp}: topp is not read here
+  for (int i = 0; temperature && i < n_rows; ++i) params[2 * i] = temperature[i];
+  HIPCHK(hipSetDevice(device));      // (left as the thread's current device, as l2_debug_running_sums leaves it)
+  const size_t elems = (size_t)n_rows * vocab;
+  float *dx = nullptr, *dt = nullptr;
+  int* dc = nullptr;
+  char* tb = nullptr;
+  double* dp = nullptr;
+  hipError_t e = hipMalloc(&dx, elems * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&dt, elems * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&dc, elems * sizeof(int));
+  if (e == hipSuccess) e = hipMemset(dc, 0, elems * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&tb, sp.h.size());
+  if (e == hipSuccess) e = hipMalloc(&dp, params.size() * sizeof(double));
+  if (e == hipSuccess) e = hipMemcpy(dx, logits, elems * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(tb, sp.h.data(), sp.h.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dp, params.data(), params.size() * sizeof(double), hipMemcpyHostToDevice);
+  rc = L2_OK;
+  if (e == hipSuccess) {
+    const ControlArgs xa = sc_args(dx, dt, tb, sp, dc, dp, vocab);
+    if (sp.penalise) rc = sc_enqueue_penalties(xa, n_rows, nullptr);
+    if (!rc) rc = sc_enqueue_truncation(xa, n_rows, nullptr);
+    if (!rc) e = hipDeviceSynchronize();
+    if (!rc && e == hipSuccess && penalised_out) e = hipMemcpy(penalised_out, dx, elems * sizeof(float), hipMemcpyDeviceToHost);
+    if (!rc && e == hipSuccess && truncated_out) e = hipMemcpy(truncated_out, dt, elems * sizeof(float), hipMemcpyDeviceToHost);
+  }
+  hipFree(dx); hipFree(dt); hipFree(dc); hipFree(tb); hipFree(dp);
+  if (rc) return rc;
+  if (e != hipSuccess) return fail(L2_E_HIP, "sample controls: %s", hipGetErrorString(e));
+  return L2_OK;
 }
 
 extern "C" int l2_read_seq_cache(l2_ctx* c, int seq, int which, int layer, float* out, size_t n_floats) {

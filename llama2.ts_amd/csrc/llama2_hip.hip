@@ -36,6 +36,7 @@
 #include "fork.hip.h"
 #include "logprob.hip.h"
 #include "constrain.hip.h"
+#include "controls.hip.h"
 #include "sampler.h"
 #include "aql_queue.h"
 

@@ -39,7 +39,12 @@ ABI_SYMBOLS = ["l2_abi_version", "l2_device_count", "l2_last_error", "l2_create"
                "l2_timer_stop", "l2_bench_gemv", "l2_bench_decode", "l2_load_checkpoint", "l2_get_header", "l2_prefill", "l2_bench_dominant_in_situ", "l2_tp_mode", "l2_create_ex", "l2_bench_tokens", "l2_dispatch_reason",
                "l2_seq_reserve", "l2_seq_prefill", "l2_forward_batch", "l2_decode_greedy_batch", "l2_read_seq_cache",
                "l2_decode_sample_batch", "l2_seq_prefill_batch", "l2_step_batch", "l2_seq_score_batch", "l2_step_batch_logprobs",
-               "l2_seq_fork", "l2_step_batch_constrained"]
+               "l2_seq_fork", "l2_step_batch_constrained", "l2_step_batch_sampling", "l2_debug_sample_controls"]
+
+
+class SampleControls(C.Structure):
+    """l2_sample_controls of include/llama2_hip.h: seven arrays that follow a call's rows, NULL for "off"."""
+    _fields_ = [(name, C.c_void_p) for name in ("hist_count", "hist_ids", "repetition", "presence", "frequency", "sample_top_k", "min_p")]
 
 
 class L2Error(RuntimeError):
@@ -106,6 +111,8 @@ def lib():
     L.l2_step_batch_logprobs.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     L.l2_seq_fork.argtypes = [vp, i32, i32, vp, i32]
     L.l2_step_batch_constrained.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.l2_step_batch_sampling.argtypes = L.l2_step_batch_constrained.argtypes + [C.POINTER(SampleControls)]
+    L.l2_debug_sample_controls.argtypes = [i32, i32, i32, vp, vp, C.POINTER(SampleControls), vp, vp]
     for name in ABI_SYMBOLS:   # fail at load time, not at first use, if the .so is stale
         getattr(L, name)
     _lib = L
@@ -157,6 +164,47 @@ def running_sums(values, device=0):
     out = np.empty(v.size, dtype=np.float64)
     _check(lib().l2_debug_running_sums(int(device), v.ctypes.data, v.size, out.ctypes.data))
     return out
+
+
+def sample_controls(n, history=None, repetition_penalty=None, presence_penalty=None, frequency_penalty=None, top_k=None, min_p=None):
+    """The l2_sample_controls of n rows from per-row lists (None, or one entry per row with None for "off"); returns (struct, the
+    arrays it points into: keep them alive as long as the struct is used)."""
+    def column(vals, dtype, off, what):
+        if vals is None:
+            return None
+        vals = list(vals)
+        if len(vals) != n:
+            raise ValueError("one %s entry per row" % what)
+        return np.array([off if v is None else v for v in vals], dtype=dtype)
+
+    cnt = ids = None
+    if history is not None:
+        history = list(history)
+        if len(history) != n:
+            raise ValueError("one history entry per row")
+        hs = [np.zeros(0, dtype=np.int32) if h is None else np.ascontiguousarray(h, dtype=np.int32).reshape(-1) for h in history]
+        cnt = np.array([h.size for h in hs], dtype=np.int32)
+        ids = np.ascontiguousarray(np.concatenate(hs), dtype=np.int32) if n else np.zeros(0, dtype=np.int32)
+    cols = [cnt, ids, column(repetition_penalty, np.float64, 1.0, "repetition_penalty"), column(presence_penalty, np.float64, 0.0, "presence_penalty"),
+            column(frequency_penalty, np.float64, 0.0, "frequency_penalty"), column(top_k, np.int32, 0, "top_k"), column(min_p, np.float64, 0.0, "min_p")]
+    return SampleControls(*[None if a is None or (a is ids and a.size == 0) else a.ctypes.data for a in cols]), cols
+
+
+def debug_sample_controls(logits, temperature=None, history=None, repetition_penalty=None, presence_penalty=None, frequency_penalty=None,
+                          top_k=None, min_p=None, device=0):
+    """The penalty and truncation launches of l2_step_batch_sampling on caller-supplied rows, with no model (l2_debug_sample_controls):
+    returns (penalised, truncated), each shaped like `logits` (n_rows, vocab).  The keywords are step_batch's."""
+    x = np.ascontiguousarray(logits, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("logits: (n_rows, vocab)")
+    n, V = x.shape
+    temp = None if temperature is None else np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, dtype=np.float64), (n,)))
+    sc, keep = sample_controls(n, history, repetition_penalty, presence_penalty, frequency_penalty, top_k, min_p)
+    pen, tr = np.empty_like(x), np.empty_like(x)
+    _check(lib().l2_debug_sample_controls(int(device), n, V, x.ctypes.data, None if temp is None else temp.ctypes.data, C.byref(sc),
+                                          pen.ctypes.data, tr.ctypes.data))
+    del keep
+    return pen, tr
 
 
 def readConfig(buf):
@@ -322,7 +370,8 @@ class Context:
                                         tlp.ctypes.data if k > 0 else None))
         return lp, am, ids, tlp
 
-    def step_batch(self, seqs, runs, pos0, temperature=0.0, topp=1.0, rng=None, logits=False, logprobs=None, allowed=None, logit_bias=None):
+    def step_batch(self, seqs, runs, pos0, temperature=0.0, topp=1.0, rng=None, logits=False, logprobs=None, allowed=None, logit_bias=None,
+                   history=None, repetition_penalty=None, presence_penalty=None, frequency_penalty=None, top_k=None, min_p=None):
         """One mixed step: feed runs[i] into sequence seqs[i] at pos0[i].. (a run of one token is a decode row), then one pick per row
         from its run's last-position logits, made on the device (temperature 0: argmax, no draw; else one xorshift* draw from rng[i]).
         temperature / topp: a scalar or one per row; rng: one state per row (uint64), or None when every row is greedy.  Returns
@@ -330,7 +379,10 @@ class Context:
         each pick's fp64 log-probability under the unscaled logits, and the k largest logits' ids / lps per row ((n, k) arrays).
         allowed: None, or per row None / an iterable of ids / a bool array of V -- the only tokens the row may pick; logit_bias: None,
         or per row None / a {id: value} dict added to those logits (l2_step_batch_constrained: the pick, the returned logits and the
-        log-probabilities are all those of the constrained row).  Identical masks are uploaded once."""
+        log-probabilities are all those of the constrained row).  Identical masks are uploaded once.
+        history, repetition_penalty, presence_penalty, frequency_penalty, top_k, min_p: None, or per row None for "off" / the row's
+        token ids already seen, its penalties on them (applied to the logits before the bias and the mask: visible like those), and
+        its sampler-only truncations (l2_step_batch_sampling, called only when one of these is given)."""
         s = np.ascontiguousarray(seqs, dtype=np.int32).reshape(-1)
         n = s.size
         rs = [np.ascontiguousarray(r, dtype=np.int32).reshape(-1) for r in runs]
@@ -352,17 +404,25 @@ class Context:
             if st.size != n:
                 raise ValueError("one rng state per row")
         ptr = lambda a: None if a is None else a.ctypes.data
-        if allowed is not None or logit_bias is not None:
+        controls = (history, repetition_penalty, presence_penalty, frequency_penalty, top_k, min_p)
+        with_controls = any(v is not None for v in controls)
+        if allowed is not None or logit_bias is not None or with_controls:
             k = 0 if logprobs is None else int(logprobs)
             plp = None if logprobs is None else np.empty(n, dtype=np.float64)
             ids = np.empty((n, max(k, 0)), dtype=np.int32)
             tlp = np.empty((n, max(k, 0)), dtype=np.float64)
             mask_of, masks, bcount, bids, bvals = self._constraints(n, allowed, logit_bias)
-            _check(lib().l2_step_batch_constrained(self._h, n, s.ctypes.data, nt.ctypes.data, tok.ctypes.data, p0.ctypes.data,
-                                                   None if st is None else temp.ctypes.data, None if st is None else tp.ctypes.data, ptr(st),
-                                                   picks.ctypes.data, ptr(out), k, ptr(plp), ids.ctypes.data if k > 0 else None,
-                                                   tlp.ctypes.data if k > 0 else None, ptr(mask_of), 0 if masks is None else len(masks),
-                                                   ptr(masks), ptr(bcount), ptr(bids), ptr(bvals)))
+            args = (self._h, n, s.ctypes.data, nt.ctypes.data, tok.ctypes.data, p0.ctypes.data,
+                    None if st is None else temp.ctypes.data, None if st is None else tp.ctypes.data, ptr(st),
+                    picks.ctypes.data, ptr(out), k, ptr(plp), ids.ctypes.data if k > 0 else None,
+                    tlp.ctypes.data if k > 0 else None, ptr(mask_of), 0 if masks is None else len(masks),
+                    ptr(masks), ptr(bcount), ptr(bids), ptr(bvals))
+            if with_controls:
+                sc, keep = sample_controls(n, *controls)
+                _check(lib().l2_step_batch_sampling(*args, C.byref(sc)))
+                del keep
+            else:
+                _check(lib().l2_step_batch_constrained(*args))
             after = None if st is None else [int(v) for v in st]
             return (picks.tolist(), after) + ((out,) if logits else ()) + (((plp, ids, tlp),) if logprobs is not None else ())
         if logprobs is None:

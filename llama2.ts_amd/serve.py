@@ -24,6 +24,12 @@ context the pick continues; `logit_bias` is a {id: value} dict added to the logi
 those of the constrained rows.  A constrained pick of BOS still ends the request: allowing BOS is how a grammar says "may stop here".
 A prompt chunk whose pick is thrown away is never constrained.  The keywords reach ctx.step_batch only in a step with such a pick.
 
+A request queued by submit_sampling or submit_n with repetition_penalty / presence_penalty / frequency_penalty / top_k / min_p has
+every one of its picks made under them (include/llama2_hip.h: l2_step_batch_sampling).  The history the penalties count is every token of
+the request fed so far, this step's included, without the BOS at position 0: the prompt plus the picks.  The penalties change the row
+everything reads (kept logits and logprobs are the penalised row's); top_k and min_p change only what a sampling pick is drawn from.
+A thrown-away pick carries none of them, and the keywords reach ctx.step_batch only in a step that holds a real pick of such a request.
+
 Scheduler(ctx, ..., prefix_cache=True) does not feed a prompt prefix whose cache rows the device already holds (a cache row of position
 p depends on tokens 0 .. p only).  The scheduler remembers per slot the tokens whose rows it holds (`resident`: what was fed since the
 slot's last restart; a finished request's rows stay until the slot is restarted).  A request with known tokens K = [BOS] + prompt may
@@ -58,7 +64,8 @@ class Result:
 
 
 class _Request:
-    def __init__(self, rid, prompt, steps, temperature, topp, seed, logprobs=None, allowed=None, logit_bias=None):
+    def __init__(self, rid, prompt, steps, temperature, topp, seed, logprobs=None, allowed=None, logit_bias=None,
+                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, top_k=0, min_p=0.0):
         self.rid = rid
         stop = prompt.index(BOS) if BOS in prompt else -1      # a forced BOS ends the reference's loop there (llama2.ts:497)
         self.prompt = prompt if stop < 0 else prompt[:stop]
@@ -73,6 +80,8 @@ class _Request:
         self.logprobs = []
         self.allowed = allowed if allowed is None or callable(allowed) else [int(t) for t in allowed]
         self.logit_bias = dict(logit_bias) if logit_bias else None
+        self.repetition, self.presence, self.frequency = float(repetition_penalty), float(presence_penalty), float(frequency_penalty)
+        self.top_k, self.min_p = int(top_k), float(min_p)
         self.leader = None                      # submit_n with prefix_cache: the sample that feeds the prompt this one waits for
         self.done = False
 
@@ -80,6 +89,10 @@ class _Request:
     def reuse_limit(self):
         """Rows a request may take from a cache: every known token that will be fed, but the last."""
         return min(len(self.known), self.steps) - 1
+
+    @property
+    def penalised(self):
+        return self.repetition != 1.0 or self.presence != 0.0 or self.frequency != 0.0
 
     @property
     def in_prompt(self):
@@ -135,20 +148,29 @@ class Scheduler:
         (see the module's text)."""
         return self._submit(prompt_ids, steps, temperature, topp, seed, logprobs, allowed, logit_bias).rid
 
-    def submit_n(self, prompt_ids, steps, seeds, temperature=0.0, topp=1.0, logprobs=None, allowed=None, logit_bias=None):
+    def submit_sampling(self, prompt_ids, steps, temperature=0.0, topp=1.0, seed=1, logprobs=None, allowed=None, logit_bias=None,
+                        repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, top_k=0, min_p=0.0):
+        """submit_constrained() with sampling controls on every pick of the request: penalties on the tokens fed so far (1 / 0 / 0:
+        off), and for a sampling request top_k (0: off) and min_p (0: off); see the module's text."""
+        return self._submit(prompt_ids, steps, temperature, topp, seed, logprobs, allowed, logit_bias,
+                            (repetition_penalty, presence_penalty, frequency_penalty, top_k, min_p)).rid
+
+    def submit_n(self, prompt_ids, steps, seeds, temperature=0.0, topp=1.0, logprobs=None, allowed=None, logit_bias=None,
+                 repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, top_k=0, min_p=0.0):
         """Queue len(seeds) samples of one prompt, each a request of its own with its own rng state; returns their ids.  With
         prefix_cache the first is admitted as any request; the others become admissible once its prompt rows are resident (all of
         [BOS] + prompt but the last token) and take them by one fork.  Once the first has fed its prompt they are ordinary waiting
         requests: if its rows are gone when a slot comes free, they feed the prompt themselves."""
         reqs = []
         for seed in seeds:
-            r = self._submit(prompt_ids, steps, temperature, topp, seed, logprobs, allowed, logit_bias)
+            r = self._submit(prompt_ids, steps, temperature, topp, seed, logprobs, allowed, logit_bias,
+                             (repetition_penalty, presence_penalty, frequency_penalty, top_k, min_p))
             if reqs and self.prefix_cache:
                 r.leader = reqs[0]
             reqs.append(r)
         return [r.rid for r in reqs]
 
-    def _submit(self, prompt_ids, steps, temperature, topp, seed, logprobs, allowed=None, logit_bias=None):
+    def _submit(self, prompt_ids, steps, temperature, topp, seed, logprobs, allowed=None, logit_bias=None, controls=(1.0, 0.0, 0.0, 0, 0.0)):
         steps = int(steps)
         if steps < 0 or steps > self.seq_len:
             raise ValueError("steps %d outside [0, seq_len=%d]" % (steps, self.seq_len))
@@ -156,7 +178,14 @@ class Scheduler:
             raise ValueError("temperature / topp is NaN")
         if logprobs is not None and not 0 <= int(logprobs) <= 20:
             raise ValueError("logprobs %d outside [0, 20]" % int(logprobs))
-        r = _Request(self._next_id, [int(t) for t in prompt_ids], steps, temperature, topp, seed, logprobs, allowed, logit_bias)
+        rep, pres, freq, top_k, min_p = controls
+        if not (0.0 < rep < float("inf")) or not all(abs(v) < float("inf") for v in (pres, freq)):
+            raise ValueError("repetition_penalty must be positive and finite, presence_penalty / frequency_penalty finite")
+        if int(top_k) < 0 or not 0.0 <= min_p <= 1.0:
+            raise ValueError("top_k %r < 0 or min_p %r outside [0, 1]" % (top_k, min_p))
+        if (int(top_k) > 0 or min_p > 0.0) and temperature < 0.0:
+            raise ValueError("top_k / min_p with a negative temperature")
+        r = _Request(self._next_id, [int(t) for t in prompt_ids], steps, temperature, topp, seed, logprobs, allowed, logit_bias, *controls)
         self._next_id += 1
         self.waiting.append(r)
         return r
@@ -270,6 +299,18 @@ class Scheduler:
             extra["allowed"] = masks
         if any(b is not None for b in bias):
             extra["logit_bias"] = bias
+        # sampling controls of the real picks: the history is what the request has fed after BOS, this step's tokens included
+        pen = [real and r.penalised for r, _, _, real in rows]
+        if any(pen):
+            extra["history"] = [(r.fed + t)[1:] if on else None for (r, t, _, _), on in zip(rows, pen)]
+            for key, attr, off in (("repetition_penalty", "repetition", 1.0), ("presence_penalty", "presence", 0.0), ("frequency_penalty", "frequency", 0.0)):
+                col = [getattr(r, attr) if on and getattr(r, attr) != off else None for (r, _, _, _), on in zip(rows, pen)]
+                if any(v is not None for v in col):
+                    extra[key] = col
+        for key, attr in (("top_k", "top_k"), ("min_p", "min_p")):
+            col = [getattr(r, attr) if real and r.temperature != 0.0 and getattr(r, attr) > 0 else None for r, _, _, real in rows]
+            if any(v is not None for v in col):
+                extra[key] = col
         out = self.ctx.step_batch(seqs, [t for _, t, _, _ in rows], [p for _, _, p, _ in rows], temperature=temp, topp=topp, rng=rng,
                                   logits=self.keep_logits, **extra)
         self.calls += 1
